@@ -13,6 +13,12 @@ on a synthetic batch of B x 1024 x 3 clouds already resident in HBM; no optimize
 (that is the metric's definition: "fwd+bwd").  Workload = BASELINE.json configs[1]: B = 32 per GPU,
 1024 -> 64 points, K = 8 (weak scaling: every rank processes its own B = 32 shard of the global batch).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  Everything else -- the roofline
+kernel probes, the secondary legs (module surface, BASELINE configs[1] / [3] / [4], batch sweep), the cpu_baseline, the
+all-reduce timed alone, the committed-profile provenance -- runs only under --full (the --no-* switches then trim it).
+--dump-outputs DIR writes what the last timed step computed (loss, simplified and projected clouds, every parameter
+gradient) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -26,7 +32,8 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MIN_TIMED_S = 0.25  # the timed region never ends sooner, whatever --steps says (blocks of K steps are added)
+MIN_TIMED_S = 0.0  # --min-time default: none, --steps is the number of timed steps (a positive value adds blocks of K steps)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all (larger arrays are replaced by a fixed, seeded sample)
 
 
 def self_launch(n, argv):
@@ -809,12 +816,50 @@ def pmc_traffic_step():
     return None
 
 
+def step_outputs(train_step, net, loss):
+    """What a caller of the timed path receives from its last step: the loss, the simplified (B,3,M) and projected (B,M,3)
+    clouds and the gradient of every parameter (views of the flat bucket, averaged over the ranks when N > 1)."""
+    out = {"loss": loss, "simplified": train_step.outputs[0], "projected": train_step.outputs[1]}
+    for name, p in net.named_parameters():
+        if p.grad is not None:
+            out["grad." + name] = p.grad
+    return out
+
+
+def dump_outputs(path, tensors, budget=DUMP_BUDGET_BYTES):
+    """Writes every tensor as path/<name>.npy in float32 (float64 stays float64).  Past `budget` bytes in all, each array is
+    replaced by the same fixed, seeded sample of its flattened entries (sorted indices), so the files stay comparable."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    room = budget - 1024 * len(arrays)  # (less a generous .npy header per file)
+    for name, a in arrays.items():
+        if total > room:
+            keep = max(1, int(a.size * room / total))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=32, help="clouds per GPU (BASELINE config: 32)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline kernel probes, the secondary legs, cpu_baseline, the all-reduce timed alone "
+                         "and the profile provenance (off: the plain run times the steps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, simplified / projected clouds, parameter "
+                         "gradients) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch the step kernel by kernel instead of replaying a hipGraph")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for the cpu_baseline leg")
@@ -826,10 +871,12 @@ def main():
                          "the first three are each captured and timed for 20 replays at start-up, the fastest is kept")
     ap.add_argument("--overlap-allreduce", action="store_true", help="same as --allreduce split")
     ap.add_argument("--no-probes", action="store_true",
-                    help="profiling runs: only the timed steps (no roofline kernel probes, no cpu_baseline, no secondary legs)")
+                    help="profiling runs: only the timed steps (no roofline kernel probes, no cpu_baseline, no secondary legs; with "
+                         "--full the all-reduce is still timed alone)")
     ap.add_argument("--force-collective", action="store_true",
                     help="world size 1: still issue the gradient all-reduce (single-GPU exercise of the RCCL path)")
-    ap.add_argument("--min-time", type=float, default=MIN_TIMED_S, help="minimum length of the timed region in seconds")
+    ap.add_argument("--min-time", type=float, default=MIN_TIMED_S,
+                    help="minimum length of the timed region in seconds (default 0: exactly --steps timed steps)")
     ap.add_argument("--only-leg", default=None, help="debugging: run only this secondary leg besides the headline")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no measurement: the N ranks only rendezvous (gloo, CPU), all-reduce their ranks and rank 0 prints a JSON "
@@ -882,7 +929,7 @@ def main():
     def step(i):
         return train_step.replay(i % len(pool))
 
-    # warm-up (also the estimate that sizes the timed region: never shorter than --min-time, whatever --steps says)
+    # warm-up (also the estimate that sizes the timed region when --min-time is given: never shorter than that)
     torch.cuda.synchronize()
     tw = time.perf_counter()
     for i in range(args.warmup):
@@ -914,11 +961,13 @@ def main():
         dt = float(t.item())
     assert torch.isfinite(loss).item()
     train_step.check()  # FC-chain hand-off error words (a timed-out launch would also have left a NaN loss)
-    # the gradient collective ALONE (every rank: it is a collective), outside the timed region: what one all-reduce of the flat
-    # bucket costs back to back at this world size -- the number the scaling curve is read against (a 0.18 ms step leaves no
-    # room for a fully exposed 30-40 us collective at N = 8)
+    if args.dump_outputs and rank == 0:  # (before anything else runs on the step's static outputs and gradient bucket)
+        dump_outputs(args.dump_outputs, step_outputs(train_step, net, loss))
+    # --full: the gradient collective ALONE (every rank: it is a collective), outside the timed region: what one all-reduce of
+    # the flat bucket costs back to back at this world size -- the number the scaling curve is read against (a 0.18 ms step
+    # leaves no room for a fully exposed 30-40 us collective at N = 8)
     allreduce_alone_us = None
-    if reducer.collective:
+    if args.full and reducer.collective:
         for _ in range(5):
             reducer._all_reduce_mean(reducer.flat)
         torch.cuda.synchronize()
@@ -943,14 +992,30 @@ def main():
     if train_step.allreduce_probe is not None:
         ar += " -- chosen by allreduce='auto' (ms per step at start-up, slowest rank: %s)" % ", ".join(
             "%s %.4f" % kv for kv in train_step.allreduce_probe["ms_per_step"].items())
+    ms = dt / total_steps * 1e3
+    value = world * B * total_steps / dt
+    headline = {
+        "metric": "point-clouds/sec fwd+bwd, Bx1024->64 soft-proj+Chamfer",
+        "value": value, "unit": "point-clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "timed_steps": total_steps, "timed_region_s": dt, "allreduce_alone_us": allreduce_alone_us,
+        "config": {"workload": "BASELINE configs[1]: SampleNet sampler train step (fwd + simplification/projection "
+                               "losses + bwd), B=%d per GPU, 1024->64 points, K=8, bottleneck 128; no optimizer step" % B,
+                   "batch_per_gpu": B, "global_batch": B * world, "n_in": N, "n_out": M, "group_size": K,
+                   "parallelism": "dp%d" % world, "rccl_ranks": world if reducer.collective else 0,
+                   "grad_allreduce": ar if reducer.collective else "none",
+                   "execution": "eager launches" if args.no_graph else "whole step replayed as one hipGraph",
+                   "mlp": "hand-written MFMA kernels: conv stack = fp32 via split-bf16 products (fp32-accurate), FC head = fp32 MFMA"},
+    }
     if rank == 0 and args.no_probes:
         print(json.dumps({"value": world * B * total_steps / dt, "ms_per_step": dt / total_steps * 1e3, "n_gpus": world,
                           "grad_allreduce": ar if reducer.collective else "none",
                        "allreduce_alone_us": allreduce_alone_us, "allreduce_bytes": int(reducer.flat.numel() * 4), "allreduce_alone_us": allreduce_alone_us,
                           "note": "--no-probes run"}), flush=True)
+    elif rank == 0 and not args.full:
+        print(json.dumps(headline), flush=True)
     elif rank == 0:
-        ms = dt / total_steps * 1e3
-        value = world * B * total_steps / dt
         prov = profile_provenance()
         kern_ms = time_pairscan_kernel(net, pool, K)
         alg = geometry_bytes_fwd(N, M, K) * B
@@ -1006,19 +1071,8 @@ def main():
         else:
             roofline_main = dict(heaviest, role="the heaviest kernel of the step (no live probe for the profile's longest kernel %r)"
                                  % (longest_out or {}).get("kernel"))
-        out = {
-            "metric": "point-clouds/sec fwd+bwd, Bx1024->64 soft-proj+Chamfer",
-            "value": value, "unit": "point-clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "timed_steps": total_steps, "timed_region_s": dt, "allreduce_alone_us": allreduce_alone_us,
-            "config": {"workload": "BASELINE configs[1]: SampleNet sampler train step (fwd + simplification/projection "
-                                   "losses + bwd), B=%d per GPU, 1024->64 points, K=8, bottleneck 128; no optimizer step" % B,
-                       "batch_per_gpu": B, "global_batch": B * world, "n_in": N, "n_out": M, "group_size": K,
-                       "parallelism": "dp%d" % world, "rccl_ranks": world if reducer.collective else 0,
-                       "grad_allreduce": ar if reducer.collective else "none",
-                       "execution": "eager launches" if args.no_graph else "whole step replayed as one hipGraph",
-                       "mlp": "hand-written MFMA kernels: conv stack = fp32 via split-bf16 products (fp32-accurate), FC head = fp32 MFMA"},
+        out = dict(headline)
+        out.update({
             "profile": prov,
             # `roofline`: the kernel with the LARGEST per-step time in the committed profile (the honest one -- a
             # latency chain far below either roof), measured live; the heaviest kernel and the whole step follow under their own keys
@@ -1043,7 +1097,7 @@ def main():
                           "frac": step_tf / MFMA_F32_PEAK_TFLOPS,
                           "note": "against the fp32 MFMA peak (the conv GEMMs run as split-bf16 products, ceiling %.0f; the FC "
                                   "head on the fp32 MFMA)" % MFMA_SPLIT_BF16_PEAK_TFLOPS},
-        }
+        })
         def leg(name, fn, *a, **k):
             """A secondary leg must never cost the headline line: its failure is recorded in its place."""
             if args.only_leg and args.only_leg != name:

@@ -644,6 +644,44 @@ def golden_modelnet():
     save("modelnet_reference.npz", **out)
 
 
+# EMD match matrices are stored sparse (tests/test_oracle.py match_gap): the entries r >= t only, t well under each test's bar
+# (5e-4 at 256 x 64: float32 values; 1e-2 at the configuration sizes: float16 values) -- 16 MB of float32 each otherwise
+MATCH_STORE = {"approxmatch_2x256x64": (3e-4, np.float32), "approxmatch_1x2048x2048": (5e-3, np.float16),
+               "approxmatch_1x4096x1024": (5e-3, np.float16)}
+
+
+def _sparse_match(r, t, dtype):
+    idx = np.flatnonzero(r >= t)
+    steps = np.diff(idx, prepend=0)
+    vals = r.ravel()[idx].astype(dtype)
+    qerr = np.abs(vals.astype(np.float64) - r.ravel()[idx].astype(np.float64)).max() if idx.size else 0.0
+    return {"match_steps": steps.astype(np.uint16 if steps.size == 0 or steps.max() < 65536 else np.uint32),
+            "match_values": vals, "match_qerr": np.float64(qerr), "match_t": np.float64(t)}
+
+
+def golden_compiled_reference():
+    """tests/test_oracle.py's *_matches_compiled_reference / *_vs_compiled_reference_cpu cases run on oracle/_ref -- the very
+    functions the tests run live where oracle/_ref is built -- stored for machines without the reference sources (EMD
+    match matrices in the sparse form of MATCH_STORE)."""
+    spec = importlib.util.spec_from_file_location("test_oracle", os.path.join(ROOT, "tests", "test_oracle.py"))
+    T = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(T)
+    cases = [("chamfer_%dx%dx%d" % sh, T.ref_chamfer_run(sh)) for sh in T.CHAMFER_SHAPES]
+    cases += [("selection_sort", T.ref_selection_sort_run), ("group_point", T.ref_group_point_run),
+              ("approxmatch_2x256x64", T.ref_approxmatch_run(2, 256, 64))]
+    cases += [("approxmatch_1x%dx%d" % (n, m), T.ref_approxmatch_run(1, n, m)) for n, m in ((2048, 2048), (4096, 1024))]
+    out = {}
+    for case, run in cases:
+        arrays = run(O)
+        if case in MATCH_STORE:
+            arrays.update(_sparse_match(arrays.pop("match"), *MATCH_STORE[case]))
+        for name, a in arrays.items():
+            out[case + "__" + name] = a
+    path = os.path.join(HERE, "compiled_reference.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", os.path.relpath(path, ROOT), "(%d arrays)" % len(out))
+
+
 if __name__ == "__main__":
     assert os.path.isdir(REF), "reference checkout not found: " + REF
     O.build(ref=True)
@@ -656,7 +694,7 @@ if __name__ == "__main__":
             "c2": lambda: golden_samplenet_c2(sn_mod.SampleNet), "c2clean": lambda: golden_samplenet_c2_clean(sn_mod.SampleNet),
             "c2eval": lambda: golden_samplenet_c2_eval(sn_mod.SampleNet), "nn_matching": lambda: golden_nn_matching(sputils),
             "pcrnet": lambda: golden_pcrnet(ChamferDistance), "loaders": golden_loaders, "modelnet": golden_modelnet,
-            "task": lambda: golden_samplenet_task(sn_mod.SampleNet, ChamferDistance)}
+            "task": lambda: golden_samplenet_task(sn_mod.SampleNet, ChamferDistance), "compiled": golden_compiled_reference}
     for name in (sys.argv[1:] or list(jobs)):  # python make_golden.py [job ...]   (default: all)
         jobs[name]()
     left = [p for p, _, fs in os.walk(REF) for f in fs if f.endswith(".pyc") or f == "__pycache__"]

@@ -1,6 +1,7 @@
 """CPU tests that PIN the oracle (oracle/samplenet_oracle.c):
-  * against the reference's own compiled CPU code (oracle/_ref, built from /root/reference
-    by oracle/Makefile) -- skipped where oracle/_ref is not present;
+  * against the reference's own compiled CPU code (oracle/_ref, built from the reference
+    sources by oracle/Makefile where they exist) -- run live where oracle/_ref is built, else
+    against the outputs of that same run stored in tests/golden/compiled_reference.npz;
   * against the golden vectors produced by running the reference Python modules
     (tests/golden/*.npz, generator tests/golden/make_golden.py);
   * against the known-answer tables of the reference's own __main__ tests.
@@ -9,15 +10,25 @@ import numpy as np
 import pytest
 
 
-def _need_ref(O):
-    if not O.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+COMPILED_REFERENCE = "compiled_reference.npz"
+
+
+def compiled_reference(O, golden, case, run):
+    """{name: array} of the reference's own compiled CPU code (oracle/_ref) on one test case: `run(O)` live where oracle/_ref is
+    built, else the arrays tests/golden/make_golden.py stored from that same function (keys "<case>__<name>")."""
+    if O.have_ref():
+        return run(O)
+    g = golden(COMPILED_REFERENCE)
+    out = {k[len(case) + 2:]: g[k] for k in g.files if k.startswith(case + "__")}
+    assert out, "no stored compiled-reference arrays for case %r" % case
+    return out
 
 
 # ------------------------------------------------------------------ Chamfer
-@pytest.mark.parametrize("shape", [(2, 64, 1024), (3, 100, 37), (1, 1, 1), (2, 513, 515)])
-def test_chamfer_matches_compiled_reference(oracle, shape):
-    _need_ref(oracle)
+CHAMFER_SHAPES = [(2, 64, 1024), (3, 100, 37), (1, 1, 1), (2, 513, 515)]
+
+
+def chamfer_case(shape):
     b, n, m = shape
     rng = np.random.default_rng(n * 7 + m)
     x1 = rng.random((b, n, 3), dtype=np.float32) - 0.5
@@ -25,15 +36,30 @@ def test_chamfer_matches_compiled_reference(oracle, shape):
     if n > 10 and m > 10:  # exact duplicates: lowest index must win on both sides
         x2[:, 3] = x2[:, 9]
         x1[:, 2] = x1[:, 7]
-    got = oracle.chamfer_forward(x1, x2)
-    ref = oracle.ref_chamfer_forward(x1, x2)
-    for g, r in zip(got, ref):
-        assert np.array_equal(g, r)
     gd1 = rng.standard_normal((b, n)).astype(np.float32)
     gd2 = rng.standard_normal((b, m)).astype(np.float32)
+    return x1, x2, gd1, gd2
+
+
+def ref_chamfer_run(shape):
+    def run(O):
+        x1, x2, gd1, gd2 = chamfer_case(shape)
+        d1, i1, d2, i2 = O.ref_chamfer_forward(x1, x2)
+        g1, g2 = O.ref_chamfer_backward(x1, x2, gd1, i1, gd2, i2)
+        return {"dist1": d1, "idx1": i1, "dist2": d2, "idx2": i2, "gxyz1": g1, "gxyz2": g2}
+    return run
+
+
+@pytest.mark.parametrize("shape", CHAMFER_SHAPES)
+def test_chamfer_matches_compiled_reference(oracle, golden, shape):
+    x1, x2, gd1, gd2 = chamfer_case(shape)
+    ref = compiled_reference(oracle, golden, "chamfer_%dx%dx%d" % shape, ref_chamfer_run(shape))
+    got = oracle.chamfer_forward(x1, x2)
+    for g, name in zip(got, ("dist1", "idx1", "dist2", "idx2")):
+        assert np.array_equal(g, ref[name])
+    # (the reference's backward ran on its own indices, asserted equal to the oracle's just above)
     g = oracle.chamfer_backward(x1, x2, gd1, got[1], gd2, got[3])
-    r = oracle.ref_chamfer_backward(x1, x2, gd1, got[1], gd2, got[3])
-    assert np.array_equal(g[0], r[0]) and np.array_equal(g[1], r[1])
+    assert np.array_equal(g[0], ref["gxyz1"]) and np.array_equal(g[1], ref["gxyz2"])
 
 
 @pytest.mark.parametrize("tag", ["a", "b", "c"])
@@ -70,14 +96,22 @@ def test_selection_sort_toy_vector(oracle):
         assert np.array_equal(oi, ri) and np.array_equal(ov, rv)
 
 
-def test_selection_sort_matches_compiled_reference(oracle):
-    _need_ref(oracle)
+def selection_sort_case():
     rng = np.random.default_rng(11)
     dist = rng.random((2, 5, 40), dtype=np.float32)
     dist[:, :, 7] = dist[:, :, 3]  # ties
-    oi, ov = oracle.selection_sort(dist, 9)
-    ri, rv = oracle.ref_selection_sort(dist, 9)
-    assert np.array_equal(oi, ri) and np.array_equal(ov, rv)
+    return dist
+
+
+def ref_selection_sort_run(O):
+    ri, rv = O.ref_selection_sort(selection_sort_case(), 9)
+    return {"idx": ri, "val": rv}
+
+
+def test_selection_sort_matches_compiled_reference(oracle, golden):
+    ref = compiled_reference(oracle, golden, "selection_sort", ref_selection_sort_run)
+    oi, ov = oracle.selection_sort(selection_sort_case(), 9)
+    assert np.array_equal(oi, ref["idx"]) and np.array_equal(ov, ref["val"])
 
 
 @pytest.mark.parametrize("k", [1, 7, 8, 16])
@@ -103,14 +137,24 @@ def test_knn_contract_on_ties(oracle):
 
 
 # ------------------------------------------------------------------ group_point
-def test_group_point_matches_compiled_reference(oracle):
-    _need_ref(oracle)
+def group_point_case():
     rng = np.random.default_rng(2)
     pts = rng.random((3, 50, 6), dtype=np.float32)
     idx = rng.integers(0, 50, (3, 11, 4)).astype(np.int32)
-    assert np.array_equal(oracle.group_point(pts, idx), oracle.ref_group_point(pts, idx))
     go = rng.random((3, 11, 4, 6), dtype=np.float32)
-    assert np.array_equal(oracle.group_point_grad(pts.shape, idx, go), oracle.ref_group_point_grad(pts.shape, idx, go))
+    return pts, idx, go
+
+
+def ref_group_point_run(O):
+    pts, idx, go = group_point_case()
+    return {"out": O.ref_group_point(pts, idx), "grad": O.ref_group_point_grad(pts.shape, idx, go)}
+
+
+def test_group_point_matches_compiled_reference(oracle, golden):
+    ref = compiled_reference(oracle, golden, "group_point", ref_group_point_run)
+    pts, idx, go = group_point_case()
+    assert np.array_equal(oracle.group_point(pts, idx), ref["out"])
+    assert np.array_equal(oracle.group_point_grad(pts.shape, idx, go), ref["grad"])
 
 
 def test_group_point_numeric_gradient(oracle):
@@ -189,49 +233,77 @@ def test_softproj_matches_reference_module(oracle, golden, tag):
 
 
 # ------------------------------------------------------------------ EMD
-def test_approxmatch_vs_compiled_reference_cpu(oracle):
+def approxmatch_case(b, n, m):
+    rng = np.random.default_rng(101)
+    return rng.random((b, n, 3), dtype=np.float32), rng.random((b, m, 3), dtype=np.float32)
+
+
+def ref_approxmatch_run(b, n, m):
+    """The reference's double-precision CPU functions: match (b, n, m) [k*m+l layout], its cost and the gradient wrt xyz2."""
+    def run(O):
+        x1, x2 = approxmatch_case(b, n, m)
+        r = O.ref_approxmatch_cpu(x1, x2)
+        return {"match": r, "cost": O.ref_matchcost_cpu(x1, x2, r), "grad2": O.ref_matchcostgrad_cpu(x1, x2, r)}
+    return run
+
+
+def match_gap(ref, mo):
+    """max |mo - r| between the oracle's match mo and the reference's r, both (b, n, m).  Exact where `ref` holds the whole r (a
+    live oracle/_ref run).  From the stored form an UPPER BOUND: only the entries r >= t are stored (flat indices as steps,
+    values with their largest rounding error qerr); every other entry lies in [0, t), where |mo - r| <= max(mo, t) for mo >= 0
+    and <= t - mo otherwise.  A bar met by the bound is met by the exact gap."""
+    if "match" in ref:
+        return float(np.abs(mo.astype(np.float64) - ref["match"].astype(np.float64)).max())
+    flat = mo.astype(np.float64).ravel()
+    idx = np.cumsum(ref["match_steps"].astype(np.int64))
+    t, qerr = float(ref["match_t"]), float(ref["match_qerr"])
+    gap = float(np.abs(flat[idx] - ref["match_values"].astype(np.float64)).max()) + qerr if idx.size else 0.0
+    rest = np.ones(flat.size, bool)
+    rest[idx] = False
+    if rest.any():
+        gap = max(gap, float(np.where(flat[rest] >= 0, np.maximum(flat[rest], t), t - flat[rest]).max()))
+    return gap
+
+
+def test_approxmatch_vs_compiled_reference_cpu(oracle, golden):
     """The fp32 oracle (the GPU op's algorithm: 10 levels, single precision) against the reference's own double-precision CPU
     functions compiled from approxmatch.cpp.  The reference's bar for this comparison is 1e-2 per entry
     (approxmatch.cpp:216-226); what the oracle actually holds -- and what oracle/README.md and DESIGN.md 2 state -- is
     5e-4 per entry (measured 3.8e-4 here; single vs double precision through 10 auction levels), 1e-6 on the cost.
     Data recipe approxmatch.cpp:131-144 (uniform(0,1), n = 4 m), shrunk so it runs in seconds."""
-    _need_ref(oracle)
-    rng = np.random.default_rng(101)
-    x1 = rng.random((2, 256, 3), dtype=np.float32)
-    x2 = rng.random((2, 64, 3), dtype=np.float32)
+    x1, x2 = approxmatch_case(2, 256, 64)
+    ref = compiled_reference(oracle, golden, "approxmatch_2x256x64", ref_approxmatch_run(2, 256, 64))
     m = oracle.approxmatch(x1, x2)
-    r = oracle.ref_approxmatch_cpu(x1, x2)
-    assert np.abs(m - r.transpose(0, 2, 1)).max() < 5e-4
+    assert match_gap(ref, m.transpose(0, 2, 1)) < 5e-4
     np.testing.assert_allclose(m.sum(1), 1.0, atol=1e-3)   # each xyz1 point ships mass 1
     np.testing.assert_allclose(m.sum(2), 4.0, atol=1e-3)   # each xyz2 point receives n/m
-    np.testing.assert_allclose(oracle.matchcost(x1, x2, m), oracle.ref_matchcost_cpu(x1, x2, r), rtol=5e-6)
+    np.testing.assert_allclose(oracle.matchcost(x1, x2, m), ref["cost"], rtol=5e-6)
     g1, g2 = oracle.matchcost_grad(x1, x2, m)
-    np.testing.assert_allclose(g2, oracle.ref_matchcostgrad_cpu(x1, x2, r), atol=1e-3)
+    np.testing.assert_allclose(g2, ref["grad2"], atol=1e-3)
 
 
 @pytest.mark.parametrize("n,m", [(2048, 2048), (4096, 1024)])
-def test_approxmatch_vs_compiled_reference_cpu_at_configuration_sizes(oracle, n, m):
+def test_approxmatch_vs_compiled_reference_cpu_at_configuration_sizes(oracle, golden, n, m):
     """The same pin at the sizes that matter: BASELINE configs[3] (n = m = 2048) and the reference harness's own shape
     (n = 4096, m = 1024: approxmatch.cpp:131-144), under the reference's OWN bars for this comparison: |match| <= 1e-2 per entry
     (approxmatch.cpp:216-226), cost <= 1e-5 relative.  The fp32-vs-fp64 gap grows with the cloud size (ten auction levels, the
     first at exp(-16384 d^2)): 4e-4 at 256 x 64, 2e-3 ... 8e-3 at these sizes depending on the draw (measured below and
     printed; the judge's draw of round 5 gave 8.3e-3 / 3.1e-3) -- the 5e-4 of the small case does NOT carry over.  The cost,
-    which is what the loss consumes, stays at 1e-6."""
-    _need_ref(oracle)
-    rng = np.random.default_rng(101)
-    x1 = rng.random((1, n, 3), dtype=np.float32)
-    x2 = rng.random((1, m, 3), dtype=np.float32)
+    which is what the loss consumes, stays at 1e-6.
+    (Without oracle/_ref the gap is match_gap's upper bound from the stored entries of the reference's match: the bar on the
+    exact match is then met a fortiori.)"""
+    x1, x2 = approxmatch_case(1, n, m)
+    ref = compiled_reference(oracle, golden, "approxmatch_1x%dx%d" % (n, m), ref_approxmatch_run(1, n, m))
     mo = oracle.approxmatch(x1, x2)
-    r = oracle.ref_approxmatch_cpu(x1, x2)
-    dmatch = float(np.abs(mo - r.transpose(0, 2, 1)).max())
-    co, cr = float(oracle.matchcost(x1, x2, mo)[0]), float(oracle.ref_matchcost_cpu(x1, x2, r)[0])
+    dmatch = match_gap(ref, mo.transpose(0, 2, 1))
+    co, cr = float(oracle.matchcost(x1, x2, mo)[0]), float(ref["cost"][0])
     print("EMD oracle vs compiled reference at (%d, %d): max |dmatch| %.2e, cost rel %.2e" % (n, m, dmatch, abs(co - cr) / cr))
     assert dmatch <= 1e-2
     assert abs(co - cr) <= 1e-5 * cr
     np.testing.assert_allclose(mo.sum(1), 1.0, atol=1e-3)
     np.testing.assert_allclose(mo.sum(2), float(n) / m, atol=2e-3 * n / m)
     g1, g2 = oracle.matchcost_grad(x1, x2, mo)
-    gr = oracle.ref_matchcostgrad_cpu(x1, x2, r)
+    gr = ref["grad2"]
     assert np.abs(g2 - gr).max() <= 1e-2 * max(1.0, np.abs(gr).max())
 
 

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 python -c "import bench; print(bench.csrc_sha16())" > $OUT/PROFILE_SRC_SHA
 for mode in graph after; do
-  timeout 300 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
+  timeout 300 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes --full 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
   cat $OUT/bench_n1_rccl_$mode.json
 done
 timeout 300 python bench.py --steps 1500 --warmup 100 --no-probes 2>/dev/null | tail -1 > $OUT/bench_n1_noprobes.json; cat $OUT/bench_n1_noprobes.json
@@ -83,6 +83,6 @@ python tools/summarize_emd.py $OUT $OUT 3
 # the bench line last, against THIS run's kernel stats: assemble profiles/<round>/ on the box first so that the line's
 # roofline_longest / profile.stale fields refer to the profile it is committed with
 bash tools/assemble_profile.sh $R > /dev/null 2>&1
-timeout 600 python bench.py --steps 300 --warmup 30 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 600 python bench.py --steps 300 --warmup 30 --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -c 300 $OUT/bench_n1.json; echo
 ls -la $OUT

@@ -20,7 +20,7 @@ echo "profile passes done at $(( $(date +%s) - S0 )) s"
 cd $GRAFT_REPO_ROOT
 # the bench line against THIS run's kernel stats (assembled on the box first: roofline / profile.stale refer to the profile it is committed with)
 bash tools/assemble_profile.sh $R > /dev/null 2>&1
-$T 150 python bench.py --steps 300 --warmup 30 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+$T 150 python bench.py --steps 300 --warmup 30 --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -c 200 $OUT/bench_n1.json; echo
 echo "bench done at $(( $(date +%s) - S0 )) s"
 $T 60 python bench.py --steps 1500 --warmup 100 --no-probes 2>/dev/null | tail -1 > $OUT/bench_n1_noprobes.json

@@ -41,9 +41,9 @@ $T 100 python tools/pairscan_scaling.py > $OUT/pairscan_scaling.txt 2>&1
 $T 100 python tools/batch_sweep.py 32 128 512 2048 > $OUT/batch_sweep.txt 2>/dev/null
 $T 200 python tools/surface_bench.py > $OUT/surface_bench.json 2>/dev/null
 # the module surface under data parallelism: reducer attached, RCCL all-reduce (forced at world size 1) inside the backward graph
-$T 200 python bench.py --gpus 1 --force-collective --steps 300 --warmup 30 --no-cpu-baseline --no-extra-legs 2> $OUT/bench_n1_rccl_surface.err | tail -1 > $OUT/bench_n1_rccl_surface.json
+$T 200 python bench.py --gpus 1 --force-collective --steps 300 --warmup 30 --full --no-cpu-baseline --no-extra-legs 2> $OUT/bench_n1_rccl_surface.err | tail -1 > $OUT/bench_n1_rccl_surface.json
 for mode in graph after; do
-  $T 120 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
+  $T 120 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes --full 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
 done
 $T 120 python bench.py --steps 1500 --warmup 100 --no-probes 2>/dev/null | tail -1 > $OUT/bench_n1_noprobes.json
 {
@@ -60,6 +60,6 @@ $T 120 python bench.py --steps 1500 --warmup 100 --no-probes 2>/dev/null | tail 
 } > $OUT/cotenancy_stress.txt 2>&1
 # the bench line last, against THIS run's kernel stats (assembled on the box first: roofline / profile.stale refer to the profile it is committed with)
 bash tools/assemble_profile.sh $R > /dev/null 2>&1
-$T 400 python bench.py --steps 300 --warmup 30 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+$T 400 python bench.py --steps 300 --warmup 30 --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -c 300 $OUT/bench_n1.json; echo
 ls $OUT | wc -l

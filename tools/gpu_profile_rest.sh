@@ -32,9 +32,9 @@ if [ "$PART" = a ]; then
 else
   $T 100 python tools/surface_bench.py > $OUT/surface_bench.json 2>/dev/null
   echo "surface bench done at $(( $(date +%s) - S0 )) s"
-  $T 60 python bench.py --gpus 1 --force-collective --steps 300 --warmup 30 --no-cpu-baseline --no-extra-legs 2> $OUT/bench_n1_rccl_surface.err | tail -1 > $OUT/bench_n1_rccl_surface.json
+  $T 60 python bench.py --gpus 1 --force-collective --steps 300 --warmup 30 --full --no-cpu-baseline --no-extra-legs 2> $OUT/bench_n1_rccl_surface.err | tail -1 > $OUT/bench_n1_rccl_surface.json
   for mode in graph after; do
-    $T 40 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
+    $T 40 python bench.py --gpus 1 --force-collective --allreduce $mode --steps 1500 --warmup 100 --no-probes --full 2> $OUT/bench_n1_rccl_$mode.err | tail -1 > $OUT/bench_n1_rccl_$mode.json
   done
   echo "rccl legs done at $(( $(date +%s) - S0 )) s"
 fi

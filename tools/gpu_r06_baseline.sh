@@ -8,7 +8,7 @@ S0=$(date +%s)
 $T 600 python -m pytest tests -m gpu -x -q --durations=10 > $OUT/pytest_gpu_baseline.log 2>&1
 tail -15 $OUT/pytest_gpu_baseline.log
 echo "tests done at $(( $(date +%s) - S0 )) s"
-$T 300 python bench.py --steps 300 --warmup 30 > $OUT/bench_baseline.json 2> $OUT/bench_baseline.err
+$T 300 python bench.py --steps 300 --warmup 30 --full > $OUT/bench_baseline.json 2> $OUT/bench_baseline.err
 tail -3 $OUT/bench_baseline.err
 python - <<PY
 import json
