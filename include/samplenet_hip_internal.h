@@ -270,7 +270,7 @@ int sn_bn_batch_stats_twopass(int R, int C, const float *z, const float *gamma, 
  *                             relu(scale x + shift) with coef_prev, identity when NULL), training-mode batch statistics over the R
  *                             rows -> coef (4, Co) = scale, shift, mean, invstd + running statistics as torch.nn.BatchNorm1d, and
  *                             y (R, Co) = z scale + shift.  Other shapes: SN_ERR_UNSUPPORTED (sn_linear_forward_rows + the next one).
- *   sn_bn_output_forward      any R, C % 4 == 0: training != 0: two-pass batch statistics of z (as sn_bn_batch_stats_twopass), else
+ *   sn_bn_output_forward      any R, any C: training != 0: two-pass batch statistics of z (as sn_bn_batch_stats_twopass), else
  *                             coefficients from the running statistics; then y = z scale + shift.
  *   sn_bn_output_backward     gy (R, C) -> dz (R, C), dgamma (C), dbeta (C); fixed != 0: the forward ran on running statistics
  *                             (dz = scale gy).  Sums in double, fixed order (deterministic). */

@@ -1389,6 +1389,16 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(long long n4, int C, cons
     reinterpret_cast<float4 *>(y)[i] = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
 }
 
+// the same for C % 4 != 0 (3M output features with M odd or M = 2 mod 4): rows are not float4-aligned, one element per thread
+__global__ void __launch_bounds__(256) bn_apply_scalar_kernel(long long n, int C, const float *__restrict__ z, const float *__restrict__ coef,
+                                                              float *__restrict__ y)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    y[i] = fmaf(z[i], coef[c], coef[C + c]);
+}
+
 // Backward of that output BatchNorm: gy (R, C) upstream gradient, z (R, C) its input, coef (4, C) of the forward ->
 // dz (R, C), dgamma, dbeta (C).  Batch statistics (fixed == 0):  dbeta = sum gy, dgamma = invstd sum gy (z - mean),
 // dz = k1 gy + k2 z + k3 with k1 = scale, k2 = -scale invstd dgamma / R, k3 = scale (invstd mean dgamma / R - dbeta / R) -- the
@@ -2021,13 +2031,13 @@ extern "C" int sn_layer_forward_bn_out(int R, int Ci, int Co, const float *ain, 
     return 0;
 }
 
-// BatchNorm WITHOUT activation on a short matrix z (R, C), C % 4 == 0: training != 0 -- two-pass batch statistics (as
+// BatchNorm WITHOUT activation on a short matrix z (R, C), any C: training != 0 -- two-pass batch statistics (as
 // sn_bn_batch_stats_twopass: coef, running statistics), else coefficients from the running statistics; then y = z scale + shift.
 extern "C" int sn_bn_output_forward(int R, int C, int training, const float *z, const float *gamma, const float *beta, float eps,
                                     float momentum, float *running_mean, float *running_var, long long *num_batches_tracked,
                                     float *coef, float *y, sn_stream_t stream)
 {
-    SN_REQUIRE(R >= 1 && C >= 4 && C % 4 == 0 && z && gamma && beta && coef && y, "bad argument");
+    SN_REQUIRE(R >= 1 && C >= 1 && z && gamma && beta && coef && y, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     if (training) {
         const BnFwd bn{gamma, beta, running_mean, running_var, num_batches_tracked, coef, eps, momentum, (long long)R};
@@ -2036,8 +2046,13 @@ extern "C" int sn_bn_output_forward(int R, int C, int training, const float *z, 
         SN_REQUIRE(running_mean && running_var, "eval mode needs the running statistics");
         hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((C + 63) / 64), dim3(64), 0, st, C, gamma, beta, eps, running_mean, running_var, coef);
     }
-    const long long n4 = (long long)R * C / 4;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4, C, z, coef, y);
+    if (C % 4 == 0) {
+        const long long n4 = (long long)R * C / 4;
+        hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4, C, z, coef, y);
+    } else {
+        const long long n = (long long)R * C;
+        hipLaunchKernelGGL(bn_apply_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, C, z, coef, y);
+    }
     SN_LAUNCH_CHECK();
     return 0;
 }

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from torch_mlp import torch_mlp_copy
+from torch_mlp import VARIANTS, fp64_bar, fp64_floor, rel as _rel, torch_mlp_copy
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +44,6 @@ def _acc_sums_zero(acc, nlayers=5, channels=None):
     return int(acc[:n].abs().max()) == 0
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).norm() / b.norm().clamp_min(1e-12))
-
-
 CFGS = [(4, 1024, 64, 8, 128, "bnc"), (3, 96, 12, 5, 32, "bcn"), (32, 1024, 64, 8, 128, "bnc"), (6, 130, 7, 4, 40, "bnc"),
         (70, 64, 16, 4, 128, "bnc"), (33, 1024, 64, 8, 128, "bnc"), (48, 512, 32, 8, 64, "bnc"),
         # exactly 64 rows in the FC head: the combined backward's statistics partials are one TileBig block where
@@ -80,11 +75,11 @@ def test_mlp_forward_backward_vs_torch(cfg):
     assert y_h.shape == y_r.shape == (B, 3, M)
     e_h, e_r = _rel(y_h.detach(), y_d.detach()), _rel(y_r.detach(), y_d.detach())
     # BatchNorm over a batch of only 3-6 samples in the FC head amplifies fp32 summation-order noise (~3e-4 there)
-    floor = 2e-4 if B >= 16 else 6e-4
+    floor = fp64_floor(B)
     if B >= 16:  # ONE bar: as close to the fp64 run as torch's own fp32 path (factor 2), floor 2e-4
-        assert e_h <= max(floor, 2 * e_r), (e_h, e_r)
+        assert e_h <= fp64_bar(B, e_r), (e_h, e_r)
     else:
-        assert e_h <= max(floor, 2 * e_r) or _rel(y_h.detach(), y_r.detach()) < floor, (e_h, e_r)
+        assert e_h <= fp64_bar(B, e_r) or _rel(y_h.detach(), y_r.detach()) < floor, (e_h, e_r)
     g = torch.randn_like(y_r)
     (y_h * g).sum().backward()
     (y_r * g).sum().backward()
@@ -106,9 +101,9 @@ def test_mlp_forward_backward_vs_torch(cfg):
         # B < 16: a near-tie in the max-pool can resolve to a different point in one fp32 implementation than in the other
         # (and than in fp64); the gradient routed through it then moves early-layer gradients by a few per cent.
         if B >= 16:  # ONE bar (no alternative): twice torch-fp32's own distance from the fp64 gradient, floor 2e-4
-            assert err_h <= max(floor, 2 * err_r), (n, err_h, err_r, err_hr)
+            assert err_h <= fp64_bar(B, err_r), (n, err_h, err_r, err_hr)
         else:
-            assert err_h <= max(floor, 2 * err_r) or err_hr <= 1e-1, (n, err_h, err_r, err_hr)
+            assert err_h <= fp64_bar(B, err_r) or err_hr <= 1e-1, (n, err_h, err_r, err_hr)
     for (n, bh), (_, bd) in zip(hip.named_buffers(), ref64.named_buffers()):
         if bh.dtype == torch.long:
             assert int(bh) == int(bd) == 1, n
@@ -718,15 +713,6 @@ def test_pcrnet_task_loss_matches_reference(golden):
         key = "g_" + n.replace(".", "_")
         if key in g.files:
             assert _rel(p.grad.cpu(), torch.from_numpy(g[key])) <= 2e-4, n
-
-
-VARIANTS = {
-    # reconstruction/src/samplers.py:23-38 (+ soft_projection.py:51-54): wider conv stack, two FC layers without BatchNorm
-    "reconstruction": dict(conv_widths=(64, 128, 128, 256), fc_widths=(256, 256), fc_batchnorm=False, temperature_floor=1e-2,
-                           min_sigma=0.0),
-    # classification/models/samplenet_model.py:30-108: registration widths + BatchNorm on the last FC layer
-    "classification": dict(last_fc_batchnorm=True, min_sigma=0.0),
-}
 
 
 @pytest.mark.parametrize("variant", ["reconstruction", "classification"])
