@@ -161,6 +161,17 @@ int sn_knn(int b, int n, int m, int k, const float *xyz1, int layout1, const flo
 int sn_nn_matching(int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps, float *out,
                    sn_stream_t stream);
 
+/* Farthest-point sampling: idx (B,M) int32 -- idx[b][0] = 0, then each pick the point with the largest running minimum squared
+ * distance to the points picked so far, ties to the LOWEST point index (numpy argmax; the rule of sn_nn_matching / sn_knn).
+ * Distances in fp32 as ((dx*dx + dy*dy) + dz*dz), never contracted.  Duplicate points and M > N are legal (once every
+ * distinct point is picked all distances are 0 and index 0 comes again); indices are in [0, N) for any input, NaN included.
+ * xyz: (B,N,3) or (B,3,N) by layout.  temp: sn_workspace_bytes("furthest_point_sample", B, N, M, 0) bytes -- nonzero (B*N
+ * floats) only where the shape runs the streaming path; NULL otherwise.  B = 0 or M = 0: no-op.
+ * Replaces pointnet2_utils.furthest_point_sample (call site registration/src/fps.py:35) and farthestpointsamplingLauncher /
+ * farthest_point_sample (reconstruction/external/sampling/tf_sampling_g.cu:105-170, tf_sampling.py:65-75); that kernel
+ * breaks ties by thread slot (k mod 512) first -- see INTEGRATION.md. */
+int sn_furthest_point_sample(int B, int N, int M, const float *xyz, int layout, float *temp, int *idx, sn_stream_t stream);
+
 /* Rotation of every cloud by its own quaternion: out[b][n] = qrot(quat[b], v[b][n]) with quat (B,4) in
  * (w, x, y, z) order, v / out (B,N,3) -- registration/src/quaternion.py:35-53 (qrot) as registration/main.py:569-571 uses it
  * through QuaternionTransform.rotate (qdataset.py:106-109: the quaternion expanded over the points).  backward: grad_v (B,N,3)

@@ -95,6 +95,11 @@ int sn_surface_gather_upstream(int nproj, const float *g_lsimp, const float *g_s
 /* From how many 64-row tiles per workgroup sn_conv_stack_forward_bn runs its GEMM layers as persistent weight-stationary
  * kernels (large batches; default 4, 0: never).  Returns the previous value.  A test / A-B hook: results are bit-identical. */
 int sn_conv_stack_set_persist_min_tiles(int tiles);
+/* Test / A-B hook of sn_furthest_point_sample: 0 = auto (default), 1 / 2 / 3 = force (a) one wave per cloud (N <= 2048),
+ * (b) one workgroup per cloud (N <= 16384), (c) streaming (any N).  A forced variant that cannot take the shape makes the call
+ * return SN_ERR_UNSUPPORTED.  Returns the previous value (-1 and no change for v outside 0..3).  Indices are bit-identical
+ * across the variants. */
+int sn_fps_set_variant(int v);
 int sn_step_tail_bytes(void);
 /* Names the error words of the step's FC chain launches (the `sync` buffers of sn_fc_chain_forward[_pool] /
  * sn_fc_chain_backward, either may be NULL) in a deferred-tail blob: the loss value the tail writes is NaN when a hand-off

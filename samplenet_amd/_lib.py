@@ -75,6 +75,8 @@ PROTOTYPES = {
     "sn_prefix_scatter_sum": [_i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "sn_knn": [_i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
     "sn_nn_matching": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp],
+    "sn_furthest_point_sample": [_i, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "sn_fps_set_variant": [_i],
     "sn_qrot_forward": [_i, _i, _vp, _vp, _vp, _vp],
     "sn_qrot_backward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_group_point": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

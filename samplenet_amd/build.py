@@ -23,6 +23,7 @@ SOURCES = [
     ("capi_common.cpp", []),
     ("pairscan.hip", ["-ffp-contract=off"]),
     ("geometry_ops.hip", ["-ffp-contract=off"]),
+    ("sampling.hip", ["-ffp-contract=off"]),
     # emd.hip carries HAND-WRITTEN packed fp32 instructions (inline asm, destination pair disjoint from every source: the form a
     # replayed instruction cannot get wrong) -- the assembler needs the feature, the compiler's own packing stays off through
     # the SLP vectoriser switch; tests/test_cabi_and_host.py checks the disassembly for both properties

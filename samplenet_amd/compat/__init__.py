@@ -1,11 +1,12 @@
 """Drop-ins for the two third-party CUDA packages the reference imports but does not vendor:
 
     knn_cuda.KNN                                      (KNN_CUDA 0.2 wheel, registration/Dockerfile:8)
-    pointnet2.utils.pointnet2_utils.grouping_operation (Pointnet2_PyTorch @5ff4382, registration/README.md:20)
+    pointnet2.utils.pointnet2_utils.grouping_operation / furthest_point_sample / gather_operation
+                                                      (Pointnet2_PyTorch @5ff4382, registration/README.md:20)
 
 `install()` registers them in sys.modules under those names so that the UNMODIFIED reference files
-registration/src/soft_projection.py and samplenet.py import and run on MI355X with the kernels of
-libsamplenet_hip.so underneath (level 1).
+registration/src/soft_projection.py, samplenet.py, fps.py and random_sampling.py import and run on MI355X with the kernels
+of libsamplenet_hip.so underneath (level 1).
 """
 import sys
 import types

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "fps_select.h"
 #include "sn_common.h"
 
 long long sn_emd_workspace_floats(int b, int n, int m);
@@ -31,5 +32,18 @@ extern "C" long long sn_workspace_bytes(const char *op, int B, int N, int M, int
     if (!strcmp(op, "matchcost")) return (long long)B * ((N + 255) / 256) * 4;  // per-workgroup partial sums
     if (!strcmp(op, "emd_loss"))  // level workspace + cost partials + the one-sweep form's tile partials
         return sn_emd_workspace_floats(B, N, M) * 4 + (long long)B * ((N + 255) / 256) * 4 + sn_emd_sweep2d_floats(B, N, M) * 4;
+    // furthest_point_sample: the streaming path's running minima (B*N floats); 0 where the shape runs register-resident
+    if (!strcmp(op, "furthest_point_sample")) return B > 0 && N > 0 && sn::fps_choose(B, N) == 3 ? (long long)B * N * 4 : 0;
     return 0;
+}
+
+// the farthest-point sampling variant hook lives here, next to the workspace query that reads it, so that a library linked
+// without sampling.o still resolves every symbol of this unit
+int sn::g_fps_variant = 0;
+extern "C" int sn_fps_set_variant(int v)
+{
+    const int prev = sn::g_fps_variant;
+    if (v < 0 || v > 3) return -1;
+    sn::g_fps_variant = v;
+    return prev;
 }

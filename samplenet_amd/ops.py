@@ -333,6 +333,28 @@ def nn_matching(xyz, idx, k, complete_fps=True, layout=BNC):
     return out
 
 
+def furthest_point_sample(xyz, npoint, layout=BNC):
+    """Farthest-point sampling (no gradient): xyz (B,N,3) [BNC] or (B,3,N) [BCN] -> idx (B,npoint) int32.
+
+    idx[:, 0] = 0; each later pick is the point farthest from those picked so far (fp32 squared distances, ties to the lowest
+    index; include/samplenet_hip.h).  pointnet2_utils.furthest_point_sample (registration/src/fps.py:35) and the TF op
+    farthest_point_sample(npoint, inp) (reconstruction/external/sampling/tf_sampling.py:65-75) with layout=BNC."""
+    _need_gpu(xyz)
+    xyz = _f32c(xyz.detach())
+    if xyz.dim() != 3 or xyz.shape[2 if layout == BNC else 1] != 3:
+        raise ValueError("furthest_point_sample: xyz must be (B,N,3) for BNC or (B,3,N) for BCN, got %s" % (tuple(xyz.shape),))
+    B = xyz.shape[0]
+    N = xyz.shape[1] if layout == BNC else xyz.shape[2]
+    idx = torch.empty(B, npoint, device=xyz.device, dtype=torch.int32)
+    # the running minima live in registers unless the streaming path runs (then B*N floats)
+    wsb = lib.sn_workspace_bytes(b"furthest_point_sample", B, N, npoint, 0) if B > 0 and npoint > 0 else 0
+    temp = torch.empty(wsb // 4, device=xyz.device, dtype=torch.float32) if wsb > 0 else None
+    with torch.cuda.device(xyz.device):
+        check(lib.sn_furthest_point_sample(B, N, npoint, ptr(xyz), layout, ptr(temp), ptr(idx), _stream(xyz)),
+              "sn_furthest_point_sample")
+    return idx
+
+
 def emd_matching(full_pc, gen_pc):
     """Device-side `emd_matching` of the TF sampler (classification/models/samplenet_model.py:152-167, the same three steps
     as reconstruction/src/samplenet_pointnet_ae.py:111-116): match = approx_match(full_pc, gen_pc) (B,k,N); every generated
@@ -408,6 +430,12 @@ class GroupingOperationFunction(torch.autograd.Function):
 
 group_point = GroupPointFunction.apply
 grouping_operation = GroupingOperationFunction.apply
+
+
+def gather_operation(features, idx):
+    """features (B,C,N), idx (B,npoint) int32 -> (B,C,npoint), differentiable w.r.t. features  [pointnet2 gather_operation,
+    registration/src/fps.py:39, random_sampling.py:42]: grouping_operation with one sample per point."""
+    return GroupingOperationFunction.apply(features, idx.unsqueeze(-1)).squeeze(-1)
 
 
 # --------------------------------------------------------------------------------------------- SoftProjection
