@@ -10,7 +10,10 @@
  *   - `stream` is a hipStream_t (passed as void*); work is enqueued on it and the call returns
  *     without synchronising (safe under hipGraph stream capture);
  *   - return value: 0 on success, otherwise a hipError_t value or SN_ERR_*; the text of the
- *     most recent error of the calling thread is returned by sn_last_error_string().
+ *     most recent error of the calling thread is returned by sn_last_error_string() and starts
+ *     with the name of the entry that was called;
+ *   - arguments are checked on the host before any device work: a negative size, a NULL required
+ *     pointer or a layout selector other than SN_LAYOUT_BNC / SN_LAYOUT_BCN is SN_ERR_BAD_ARGUMENT.
  *
  * Each function names the reference interface it replaces (file:line under the
  * itailang/SampleNet checkout).  THIS header is the drop-in boundary: the entries a binding of the
@@ -56,6 +59,8 @@ long long sn_workspace_bytes(const char *op, int B, int N, int M, int K);
  *   knn_idx (B,M,K) int32, knn_dist (B,M,K) squared distances.
  *   dist_q/idx_q (B,M); dist_p/idx_p (B,N).
  *   proj: soft projection, written in `proj_layout`; weights (B,M,K) optional softmax weights.
+ *         Both are held to 1e-6 of the exact value: sums over K <= 16 neighbours run in fp32 in
+ *         ascending k, longer ones accumulate in fp64 and round once.
  *   temperature: device pointer to the scalar T; sigma = max(T*T, min_sigma)
  *                (registration/src/soft_projection.py:97-99).
  * Replaces, in one launch: knn_cuda.KNN (call sites soft_projection.py:11-14, samplenet.py:121;
@@ -200,16 +205,19 @@ int sn_grouping_operation_grad(int b, int c, int n, int m, int nsample, const fl
 /* ---------------------------------------------------------------------------------------------
  * SoftProjection pieces (channel-major tensors, as the torch module uses them).
  *   sn_soft_weights_forward : w = softmax_k(-|P[idx]-Q|^2 / sigma)          soft_projection.py:92-95,143
- *   sn_soft_weights_backward: grad_w -> grad_Q (b,3,m) [overwritten], grad_P (b,3,n)
- *                             [ACCUMULATED with atomics; may be NULL], grad_sigma_partial (b)
- *                             [overwritten; sum it and apply d sigma/dT on the caller side]
+ *   sn_soft_weights_backward: grad_w -> grad_Q (b,3,m) [overwritten; may be NULL], grad_P (b,3,n)
+ *                             [ACCUMULATED with atomics; may be NULL], grad_sigma_partial
+ *                             (b * sn_soft_bwd_splits(b,m)) [overwritten; may be NULL; sum it and apply
+ *                             d sigma/dT on the caller side: sn_sigma_grad].  `weights` is not read (the
+ *                             kernel recomputes the softmax from P, Q, idx): NULL is allowed.
  *   sn_weighted_gather_forward : out[c,j] = sum_k w[j,k] X[c, idx[j,k]]      soft_projection.py:113-118,131-134,148-151
  *   sn_weighted_gather_backward: grad_out -> grad_w (b,m,k) [overwritten, may be NULL],
  *                                grad_X (b,c,n) [ACCUMULATED with atomics, may be NULL]
  *   sn_soft_project_backward   : fused backward of `project` for the hot path:
- *                                grad_proj (layout selectable) -> grad_Q (b,3,m) overwritten,
- *                                grad_sigma_partial (b * sn_soft_bwd_splits(b,m)) overwritten, grad_P optional
- *                                (atomics).  sn_soft_weights_backward: same partial count.
+ *                                grad_proj (gproj_layout) -> grad_Q (gq_layout) overwritten,
+ *                                grad_sigma_partial (b * sn_soft_bwd_splits(b,m)) overwritten, grad_P (p_layout)
+ *                                ACCUMULATED with atomics; each of the three may be NULL.
+ *   k <= 64 for the soft_weights / soft_project entries; b = 0 or m = 0: no-op.
  * ------------------------------------------------------------------------------------------- */
 int sn_soft_bwd_splits(int b, int m);
 /* d loss/dT = (sum of the grad_sigma partials) * d max(T^2, min_sigma)/dT  (soft_projection.py:97-99), one launch */

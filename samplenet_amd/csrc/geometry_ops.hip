@@ -1338,6 +1338,10 @@ extern "C" int sn_soft_project_backward(int b, int n, int m, int k, const float 
 {
     SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
     if (b == 0 || m == 0) return 0;
+    SN_REQUIRE((p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN) && (q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN),
+               "bad p_layout / q_layout");
+    SN_REQUIRE((gproj_layout == SN_LAYOUT_BNC || gproj_layout == SN_LAYOUT_BCN) && (gq_layout == SN_LAYOUT_BNC || gq_layout == SN_LAYOUT_BCN),
+               "bad gproj_layout / gq_layout");
     SN_REQUIRE(P && Q && idx && temperature && grad_proj, "null input");
     SoftBwdArgs a{};
     a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
@@ -1409,19 +1413,21 @@ extern "C" int sn_weighted_gather_backward(int b, int c, int n, int m, int k, co
 // dst (b, n, c) [or (b, c, n)] = index-add of src over idx (b, ne): ordered and deterministic up to kIndexAddOrderedWork
 // index loads per cloud, float atomics into a zeroed destination beyond
 template <bool CHANNEL_MAJOR>
-static int launch_index_add(int b, int n, int c, long long ne, const int *idx, const float *src, float *dst, hipStream_t st)
+static int launch_index_add(const char *who, int b, int n, int c, long long ne, const int *idx, const float *src, float *dst,
+                            hipStream_t st)
 {
-    SN_REQUIRE(ne <= 0x7fffffffll, "m * nsample must fit in 31 bits");
+    SN_REQUIRE_AS(who, ne <= 0x7fffffffll, "m * nsample must fit in 31 bits");
     if ((long long)((n + 63) / 64) * ne <= kIndexAddOrderedWork) {
         hipLaunchKernelGGL(index_add_ordered_kernel<CHANNEL_MAJOR>, dim3((n + 255) / 256, b), dim3(256), 0, st, n, c, (int)ne, idx,
                            src, dst);
     } else {
         const hipError_t e = hipMemsetAsync(dst, 0, (size_t)b * n * c * sizeof(float), st);
-        if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", __func__, hipGetErrorString(e));
+        if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
         hipLaunchKernelGGL(index_add_atomic_kernel<CHANNEL_MAJOR>, dim3(grid_for((size_t)ne * c), b), dim3(256), 0, st, n, c, ne,
                            idx, src, dst);
     }
-    SN_LAUNCH_CHECK();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
     return 0;
 }
 
@@ -1437,6 +1443,10 @@ extern "C" int sn_soft_project_backward_ordered(int b, int n, int m, int k, cons
 {
     SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
     if (b == 0 || m == 0) return 0;
+    SN_REQUIRE((p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN) && (q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN),
+               "bad p_layout / q_layout");
+    SN_REQUIRE((gproj_layout == SN_LAYOUT_BNC || gproj_layout == SN_LAYOUT_BCN) && (gq_layout == SN_LAYOUT_BNC || gq_layout == SN_LAYOUT_BCN),
+               "bad gproj_layout / gq_layout");
     SN_REQUIRE(P && Q && idx && temperature && grad_proj && grad_P && scratch, "null pointer");
     SoftBwdArgs a{};
     a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
@@ -1444,8 +1454,8 @@ extern "C" int sn_soft_project_backward_ordered(int b, int n, int m, int k, cons
     a.grad_proj = grad_proj, a.gproj_layout = gproj_layout;
     a.grad_Q = grad_Q, a.gq_layout = gq_layout, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
     hipLaunchKernelGGL(soft_bwd_kernel<true>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    return p_layout == SN_LAYOUT_BNC ? launch_index_add<false>(b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream)
-                                     : launch_index_add<true>(b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    return p_layout == SN_LAYOUT_BNC ? launch_index_add<false>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream)
+                                     : launch_index_add<true>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
 }
 
 extern "C" int sn_soft_weights_backward_ordered(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
@@ -1462,7 +1472,7 @@ extern "C" int sn_soft_weights_backward_ordered(int b, int n, int m, int k, cons
     a.weights_in = weights, a.grad_weights = grad_weights;
     a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
     hipLaunchKernelGGL(soft_bwd_kernel<false>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    return launch_index_add<true>(b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    return launch_index_add<true>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
 }
 
 extern "C" int sn_weighted_gather_backward_ordered(int b, int c, int n, int m, int k, const float *X, const int *idx,
@@ -1475,7 +1485,7 @@ extern "C" int sn_weighted_gather_backward_ordered(int b, int c, int n, int m, i
     hipLaunchKernelGGL(weighted_gather_bwd_kernel, dim3(((size_t)m * k + 255) / 256, b), dim3(256), 0, (hipStream_t)stream, c, n, m,
                        k, X, idx, weights, grad_out, grad_weights, grad_X, scratch);
     if (c == 0) return 0;
-    return launch_index_add<true>(b, n, c, (long long)m * k, idx, scratch, grad_X, (hipStream_t)stream);
+    return launch_index_add<true>(__func__, b, n, c, (long long)m * k, idx, scratch, grad_X, (hipStream_t)stream);
 }
 
 extern "C" int sn_group_point(int b, int n, int c, int m, int nsample, const float *points, const int *idx,
@@ -1498,7 +1508,7 @@ extern "C" int sn_group_point_grad(int b, int n, int c, int m, int nsample, cons
     if (b == 0 || (size_t)n * c == 0) return 0;
     SN_REQUIRE(grad_points, "null pointer");
     SN_REQUIRE((size_t)m * nsample == 0 || (grad_out && idx), "null pointer");
-    return launch_index_add<false>(b, n, c, (long long)m * nsample, idx, grad_out, grad_points, (hipStream_t)stream);
+    return launch_index_add<false>(__func__, b, n, c, (long long)m * nsample, idx, grad_out, grad_points, (hipStream_t)stream);
 }
 
 extern "C" int sn_grouping_operation(int b, int c, int n, int m, int nsample, const float *features,
@@ -1521,7 +1531,7 @@ extern "C" int sn_grouping_operation_grad(int b, int c, int n, int m, int nsampl
     if (b == 0 || (size_t)n * c == 0) return 0;
     SN_REQUIRE(grad_features, "null pointer");
     SN_REQUIRE((size_t)m * nsample == 0 || (grad_out && idx), "null pointer");
-    return launch_index_add<true>(b, n, c, (long long)m * nsample, idx, grad_out, grad_features, (hipStream_t)stream);
+    return launch_index_add<true>(__func__, b, n, c, (long long)m * nsample, idx, grad_out, grad_features, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -496,18 +496,24 @@ __global__ void __launch_bounds__(max_threads(PPL, COLMIN)) pairscan_kernel(Pair
                     gy = Pb[pt_off(a.p_layout, N, nidx, 1)];
                     gz = Pb[pt_off(a.p_layout, N, nidx, 2)];
                 }
-                float den = 0.f;
-                for (int t = 0; t < K; ++t) den += readlane_f(e, t);
+                // K > 16: up to 64 terms per sum.  An fp32 running sum of that length is off by up to ~8e-7 from the exact
+                // value at unit scale (as is the reference's own fp32 loop), which alone uses most of the 1e-6 the
+                // projection is held to; the products of two fp32 numbers are exact in fp64, so the denominator and the
+                // three weighted sums run in fp64 and round once at the end.
+                double dend = 0.0;
+                for (int t = 0; t < K; ++t) dend += (double)readlane_f(e, t);
+                const float den = (float)dend;
                 const float w = e / den;  // softmax over the K neighbours (:143)
                 if (a.weights && lane < K) a.weights[qrow * K + lane] = w;
                 if (a.proj) {
-                    float ox = 0.f, oy = 0.f, oz = 0.f;
-                    for (int t = 0; t < K; ++t) {  // ascending k, product then sum (:148-151)
-                        const float wt = readlane_f(w, t);
-                        ox += readlane_f(gx, t) * wt;
-                        oy += readlane_f(gy, t) * wt;
-                        oz += readlane_f(gz, t) * wt;
+                    double dx = 0.0, dy = 0.0, dz = 0.0;
+                    for (int t = 0; t < K; ++t) {  // ascending k (:148-151)
+                        const double wt = (double)readlane_f(w, t);
+                        dx += (double)readlane_f(gx, t) * wt;
+                        dy += (double)readlane_f(gy, t) * wt;
+                        dz += (double)readlane_f(gz, t) * wt;
                     }
+                    const float ox = (float)dx, oy = (float)dy, oz = (float)dz;
                     if (lane < 3) {
                         const float o = lane == 0 ? ox : (lane == 1 ? oy : oz);
                         a.proj[(size_t)b * 3 * M + pt_off(a.proj_layout, M, j, lane)] = o;
@@ -672,38 +678,24 @@ extern "C" long long sn_pairscan_workspace_bytes(int B, int N, int M)
     return ysplit > 1 ? (long long)B * ysplit * N * 8 : 0;
 }
 
-extern "C" int sn_pairscan_forward_ws(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
-                                      int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q,
-                                      float *dist_p, int *idx_p, float *proj, int proj_layout, float *weights,
-                                      const float *temperature, float min_sigma, void *workspace,
-                                      long long workspace_bytes, sn_stream_t stream);
-
-extern "C" int sn_pairscan_forward(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
-                                   int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q,
-                                   float *dist_p, int *idx_p, float *proj, int proj_layout, float *weights,
-                                   const float *temperature, float min_sigma, sn_stream_t stream)
+// the body of every public pair-scan entry; `who` names the entry in the error text
+static int pairscan_forward_impl(const char *who, int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
+                                 int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q, float *dist_p,
+                                 int *idx_p, float *proj, int proj_layout, float *weights, const float *temperature,
+                                 float min_sigma, void *workspace, long long workspace_bytes, sn_stream_t stream)
 {
-    return sn_pairscan_forward_ws(B, N, M, K, P, p_layout, Q, q_layout, knn_idx, knn_dist, dist_q, idx_q, dist_p, idx_p,
-                                  proj, proj_layout, weights, temperature, min_sigma, nullptr, 0, stream);
-}
-
-extern "C" int sn_pairscan_forward_ws(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
-                                      int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q,
-                                      float *dist_p, int *idx_p, float *proj, int proj_layout, float *weights,
-                                      const float *temperature, float min_sigma, void *workspace,
-                                      long long workspace_bytes, sn_stream_t stream)
-{
-    SN_REQUIRE(B >= 0 && N >= 0 && M >= 0 && K >= 0, "negative size");
+    SN_REQUIRE_AS(who, B >= 0 && N >= 0 && M >= 0 && K >= 0, "negative size");
     if (B == 0 || (M == 0 && N == 0)) return 0;
-    SN_REQUIRE(P && Q, "null point cloud");
-    SN_REQUIRE(N >= 1 && M >= 1, "empty cloud on one side only");
-    SN_REQUIRE(K <= N, "K exceeds the number of dataset points");
-    SN_REQUIRE(K <= 64, "K > 64 unsupported");
-    SN_REQUIRE(p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
-    SN_REQUIRE(q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN, "bad q_layout");
+    SN_REQUIRE_AS(who, P && Q, "null point cloud");
+    SN_REQUIRE_AS(who, N >= 1 && M >= 1, "empty cloud on one side only");
+    SN_REQUIRE_AS(who, K <= N, "K exceeds the number of dataset points");
+    SN_REQUIRE_AS(who, K <= 64, "K > 64 unsupported");
+    SN_REQUIRE_AS(who, p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
+    SN_REQUIRE_AS(who, q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN, "bad q_layout");
+    SN_REQUIRE_AS(who, proj_layout == SN_LAYOUT_BNC || proj_layout == SN_LAYOUT_BCN, "bad proj_layout");
     const bool knn = knn_idx || knn_dist, soft = proj || weights;
-    SN_REQUIRE(!(knn || soft) || K >= 1, "K must be >= 1 for kNN / projection outputs");
-    SN_REQUIRE(!soft || temperature, "projection needs the temperature pointer");
+    SN_REQUIRE_AS(who, !(knn || soft) || K >= 1, "K must be >= 1 for kNN / projection outputs");
+    SN_REQUIRE_AS(who, !soft || temperature, "projection needs the temperature pointer");
     hipStream_t st = (hipStream_t)stream;
     PairscanArgs a{};
     a.P = P, a.Q = Q, a.p_layout = p_layout, a.q_layout = q_layout;
@@ -726,8 +718,28 @@ extern "C" int sn_pairscan_forward_ws(int B, int N, int M, int K, const float *P
         rc = sn::pairscan_dispatch(s, nullptr, 0, true, nullptr, st);
         if (rc) return rc;
     }
-    SN_LAUNCH_CHECK();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
     return 0;
+}
+
+extern "C" int sn_pairscan_forward(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
+                                   int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q,
+                                   float *dist_p, int *idx_p, float *proj, int proj_layout, float *weights,
+                                   const float *temperature, float min_sigma, sn_stream_t stream)
+{
+    return pairscan_forward_impl(__func__, B, N, M, K, P, p_layout, Q, q_layout, knn_idx, knn_dist, dist_q, idx_q, dist_p, idx_p,
+                                 proj, proj_layout, weights, temperature, min_sigma, nullptr, 0, stream);
+}
+
+extern "C" int sn_pairscan_forward_ws(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
+                                      int q_layout, int *knn_idx, float *knn_dist, float *dist_q, int *idx_q,
+                                      float *dist_p, int *idx_p, float *proj, int proj_layout, float *weights,
+                                      const float *temperature, float min_sigma, void *workspace,
+                                      long long workspace_bytes, sn_stream_t stream)
+{
+    return pairscan_forward_impl(__func__, B, N, M, K, P, p_layout, Q, q_layout, knn_idx, knn_dist, dist_q, idx_q, dist_p, idx_p,
+                                 proj, proj_layout, weights, temperature, min_sigma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sn_chamfer_forward(int b, int n, const float *xyz, int m, const float *xyz2, float *result,
@@ -738,18 +750,19 @@ extern "C" int sn_chamfer_forward(int b, int n, const float *xyz, int m, const f
     SN_REQUIRE(n >= 1 && m >= 1, "empty cloud on one side only");
     // lanes own the larger set (it amortises the per-query filter cost); outputs map accordingly
     if (m >= n)
-        return sn_pairscan_forward(b, m, n, 0, xyz2, SN_LAYOUT_BNC, xyz, SN_LAYOUT_BNC, nullptr, nullptr, result,
-                                   result_i, result2, result2_i, nullptr, 0, nullptr, nullptr, 0.f, stream);
-    return sn_pairscan_forward(b, n, m, 0, xyz, SN_LAYOUT_BNC, xyz2, SN_LAYOUT_BNC, nullptr, nullptr, result2,
-                               result2_i, result, result_i, nullptr, 0, nullptr, nullptr, 0.f, stream);
+        return pairscan_forward_impl(__func__, b, m, n, 0, xyz2, SN_LAYOUT_BNC, xyz, SN_LAYOUT_BNC, nullptr, nullptr, result,
+                                     result_i, result2, result2_i, nullptr, 0, nullptr, nullptr, 0.f, nullptr, 0, stream);
+    return pairscan_forward_impl(__func__, b, n, m, 0, xyz, SN_LAYOUT_BNC, xyz2, SN_LAYOUT_BNC, nullptr, nullptr, result2,
+                                 result2_i, result, result_i, nullptr, 0, nullptr, nullptr, 0.f, nullptr, 0, stream);
 }
 
 extern "C" int sn_knn(int b, int n, int m, int k, const float *xyz1, int layout1, const float *xyz2, int layout2,
                       int *idx, float *dist, sn_stream_t stream)
 {
+    SN_REQUIRE(b >= 0 && n >= 0 && m >= 0, "negative size");
     SN_REQUIRE(k >= 1, "k must be >= 1");
-    return sn_pairscan_forward(b, n, m, k, xyz1, layout1, xyz2, layout2, idx, dist, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, 0, nullptr, nullptr, 0.f, stream);
+    return pairscan_forward_impl(__func__, b, n, m, k, xyz1, layout1, xyz2, layout2, idx, dist, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, 0, nullptr, nullptr, 0.f, nullptr, 0, stream);
 }
 
 // Pair scan whose per-point minima are left as PARTIAL (distance,index) keys, one set per workgroup of a cloud:

@@ -13,6 +13,13 @@ int sn_set_error(int code, const char *fmt, ...);
         if (!(cond)) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: %s", __func__, msg); \
     } while (0)
 
+// the same under the name of the public entry that forwards its arguments to a shared implementation
+#define SN_REQUIRE_AS(who, cond, msg)                                               \
+    do {                                                                            \
+        (void)hipGetLastError();                                                    \
+        if (!(cond)) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: %s", who, msg);  \
+    } while (0)
+
 // hipGetLastError() reports (and clears) the most recent error of ANY runtime call on this host
 // thread, including calls made by other libraries in the process: discard stale state on entry so
 // that SN_LAUNCH_CHECK only sees this entry point's own launches.

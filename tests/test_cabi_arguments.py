@@ -1,0 +1,194 @@
+"""Host-side half of the C-ABI contract (no GPU): every geometric entry point of include/samplenet_hip.h refuses a negative
+size, a NULL required pointer, an unknown layout selector and an unsupported K / prefix count / matching size with the
+documented code and its OWN name in sn_last_error_string(), and treats the documented empty cases as no-ops -- all of it before
+any device work.  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BAD, UNSUP = 10001, 10002
+Pp = "PTR"    # a non-NULL (never dereferenced) device pointer
+HOSTI = "HOSTI"  # a real host int array {4}: sn_prefix_point_minima reads its prefix sizes on the host
+
+# entry -> (valid argument list, positions of the sizes, positions of the REQUIRED pointers).  The valid list itself is never
+# called: every case breaks one argument of it.  Optional pointers are left NULL in the base.
+ENTRIES = {
+    "sn_pairscan_forward": ([1, 8, 4, 2, Pp, 0, Pp, 0, Pp, Pp, Pp, Pp, Pp, Pp, Pp, 0, Pp, Pp, 0.0, None], [0, 1, 2, 3], [4, 6, 17]),
+    "sn_pairscan_forward_ws": ([1, 8, 4, 2, Pp, 0, Pp, 0, Pp, Pp, Pp, Pp, Pp, Pp, Pp, 0, Pp, Pp, 0.0, None, 0, None], [0, 1, 2, 3],
+                               [4, 6, 17]),
+    "sn_chamfer_forward": ([1, 8, Pp, 4, Pp, Pp, Pp, Pp, Pp, None], [0, 1, 3], [2, 4]),
+    "sn_chamfer_backward": ([1, 8, Pp, 4, Pp, Pp, Pp, Pp, Pp, Pp, Pp, None], [0, 1, 3], [2, 4, 5, 6, 7, 8]),
+    "sn_knn": ([1, 8, 4, 2, Pp, 0, Pp, 0, Pp, Pp, None], [0, 1, 2, 3], [4, 6]),
+    "sn_soft_weights_forward": ([1, 8, 4, 2, Pp, Pp, Pp, Pp, 0.0, Pp, None], [0, 1, 2, 3], [4, 5, 6, 7, 9]),
+    "sn_soft_weights_backward": ([1, 8, 4, 2, Pp, Pp, Pp, Pp, 0.0, None, Pp, None, None, None, None], [0, 1, 2, 3], [4, 5, 6, 7, 10]),
+    "sn_soft_weights_backward_ordered": ([1, 8, 4, 2, Pp, Pp, Pp, Pp, 0.0, None, Pp, None, Pp, None, Pp, None], [0, 1, 2, 3],
+                                         [4, 5, 6, 7, 10, 12, 14]),
+    "sn_weighted_gather_forward": ([1, 3, 8, 4, 2, Pp, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7, 8]),
+    "sn_weighted_gather_backward": ([1, 3, 8, 4, 2, Pp, Pp, Pp, Pp, None, None, None], [0, 1, 2, 3, 4], [5, 6, 7, 8]),
+    "sn_weighted_gather_backward_ordered": ([1, 3, 8, 4, 2, Pp, Pp, Pp, Pp, None, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7, 8, 10, 11]),
+    "sn_soft_project_backward": ([1, 8, 4, 2, Pp, 0, Pp, 0, Pp, Pp, 0.0, Pp, 0, None, 0, None, None, None], [0, 1, 2, 3],
+                                 [4, 6, 8, 9, 11]),
+    "sn_soft_project_backward_ordered": ([1, 8, 4, 2, Pp, 0, Pp, 0, Pp, Pp, 0.0, Pp, 0, None, 0, Pp, None, Pp, None], [0, 1, 2, 3],
+                                         [4, 6, 8, 9, 11, 15, 17]),
+    "sn_sigma_grad": ([2, Pp, Pp, 0.0, Pp, None], [0], [1, 2, 4]),
+    "sn_group_point": ([1, 8, 3, 4, 2, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7]),
+    "sn_group_point_grad": ([1, 8, 3, 4, 2, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7]),
+    "sn_grouping_operation": ([1, 3, 8, 4, 2, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7]),
+    "sn_grouping_operation_grad": ([1, 3, 8, 4, 2, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7]),
+    "sn_simplification_loss_forward": ([1, 4, 8, Pp, Pp, 1.0, Pp, Pp, Pp, None], [0, 1, 2], [3, 4, 6, 7, 8]),
+    "sn_simplification_loss_backward": ([1, 4, Pp, 8, Pp, Pp, Pp, Pp, 1.0, Pp, Pp, None, 0, None], [0, 1, 3], [2, 4, 5, 6, 7, 9]),
+    "sn_chamfer_mean_loss_forward": ([1, 4, 8, Pp, Pp, Pp, Pp, Pp, None], [0, 1, 2], [3, 4, 5, 6, 7]),
+    "sn_chamfer_mean_loss_backward": ([1, 4, Pp, 8, Pp, Pp, Pp, Pp, Pp, None, None], [0, 1, 3], [2, 4, 5, 6, 7]),
+    "sn_pcrnet_head_forward": ([2, Pp, Pp, None, None, None], [0], [1, 2]),
+    "sn_pcrnet_head_backward": ([2, Pp, None, None, None, Pp, None], [0], [1, 5]),
+    "sn_qrot_forward": ([1, 8, Pp, Pp, Pp, None], [0, 1], [2, 3, 4]),
+    "sn_qrot_backward": ([1, 8, Pp, Pp, Pp, Pp, None, None], [0, 1], [2, 3, 4]),
+    "sn_prefix_point_minima": ([1, 8, 4, 1, HOSTI, Pp, Pp, Pp, Pp, None], [0, 1, 2, 3], [4, 5, 6, 7, 8]),
+    "sn_nn_matching": ([1, 8, 4, Pp, 0, Pp, 1, Pp, None], [0, 1, 2], [3, 5, 7]),
+}
+
+
+def _with(name, changes):
+    args = list(ENTRIES[name][0])
+    for pos, val in changes.items():
+        args[pos] = val
+    return args
+
+
+def _cases():
+    out = []  # (id, entry, args, expected code, text the message must contain | None)
+    for name, (base, sizes, required) in ENTRIES.items():
+        for pos in sizes:
+            out.append(("%s-size%d-negative" % (name, pos), name, _with(name, {pos: -1}), BAD, name))
+        for pos in required:
+            out.append(("%s-arg%d-null" % (name, pos), name, _with(name, {pos: None}), BAD, name))
+    # both gradient outputs NULL: sn_qrot_backward has nothing to compute
+    out.append(("sn_qrot_backward-no-output", "sn_qrot_backward", _with("sn_qrot_backward", {5: None, 6: None}), BAD, "sn_qrot_backward"))
+    # layout selectors: any value other than 0 / 1 is refused by every entry that takes one
+    for name, positions in (("sn_pairscan_forward", (5, 7, 15)), ("sn_pairscan_forward_ws", (5, 7, 15)), ("sn_knn", (5, 7)),
+                            ("sn_soft_project_backward", (5, 7, 12, 14)), ("sn_soft_project_backward_ordered", (5, 7, 12, 14)),
+                            ("sn_simplification_loss_backward", (12,)), ("sn_nn_matching", (4,))):
+        for pos in positions:
+            for bad in (2, -1):
+                out.append(("%s-selector%d-is-%d" % (name, pos, bad), name, _with(name, {pos: bad}), BAD, name))
+    out.append(("simp-bwd-layout1-with-grad_xyz2", "sn_simplification_loss_backward",
+                _with("sn_simplification_loss_backward", {12: 1, 11: Pp}), BAD, "grad_xyz2"))
+    # K / k limits
+    for name in ("sn_pairscan_forward", "sn_pairscan_forward_ws", "sn_knn"):
+        out.append((name + "-K65", name, _with(name, {1: 100, 3: 65}), BAD, name))
+        out.append((name + "-K>N", name, _with(name, {1: 4, 3: 5}), BAD, name))
+    for name in ("sn_soft_weights_forward", "sn_soft_weights_backward", "sn_soft_weights_backward_ordered", "sn_soft_project_backward",
+                 "sn_soft_project_backward_ordered"):
+        out.append((name + "-k65", name, _with(name, {1: 100, 3: 65}), BAD, name))
+        out.append((name + "-k0", name, _with(name, {3: 0}), BAD, name))
+    out.append(("sn_knn-k0", "sn_knn", _with("sn_knn", {3: 0}), BAD, "sn_knn"))
+    out.append(("pairscan-K0-with-knn-output", "sn_pairscan_forward", _with("sn_pairscan_forward", {3: 0}), BAD, "K must be >= 1"))
+    out.append(("pairscan-one-side-empty", "sn_pairscan_forward", _with("sn_pairscan_forward", {2: 0}), BAD, "empty cloud"))
+    out.append(("sn_prefix_point_minima-nprefix17", "sn_prefix_point_minima", _with("sn_prefix_point_minima", {3: 17}), BAD,
+                "sn_prefix_point_minima"))
+    out.append(("sn_prefix_point_minima-last-prefix-not-M", "sn_prefix_point_minima", _with("sn_prefix_point_minima", {2: 5}), BAD,
+                "last prefix"))
+    out.append(("sn_nn_matching-k1025", "sn_nn_matching", _with("sn_nn_matching", {1: 2000, 2: 1025}), UNSUP, "sn_nn_matching"))
+    out.append(("sn_nn_matching-N8193", "sn_nn_matching", _with("sn_nn_matching", {1: 8193}), UNSUP, "sn_nn_matching"))
+    out.append(("sn_sigma_grad-nparts0", "sn_sigma_grad", _with("sn_sigma_grad", {0: 0}), BAD, "sn_sigma_grad"))
+    for name in ("sn_simplification_loss_forward", "sn_simplification_loss_backward", "sn_chamfer_mean_loss_forward",
+                 "sn_chamfer_mean_loss_backward", "sn_pcrnet_head_forward", "sn_pcrnet_head_backward", "sn_prefix_point_minima"):
+        out.append((name + "-B0-is-an-error", name, _with(name, {0: 0}), BAD, name))  # (these take B >= 1: no empty case documented)
+    # documented empty cases: 0 with every pointer NULL
+    nulled = lambda name, ch: [None if a in (Pp, HOSTI) else a for a in _with(name, ch)]
+    for name, ch in (("sn_pairscan_forward", {0: 0}), ("sn_pairscan_forward_ws", {0: 0}), ("sn_pairscan_forward", {1: 0, 2: 0, 3: 0}),
+                     ("sn_chamfer_forward", {0: 0}), ("sn_chamfer_forward", {1: 0, 3: 0}), ("sn_knn", {0: 0}),
+                     ("sn_chamfer_backward", {0: 0}), ("sn_chamfer_backward", {1: 0}), ("sn_chamfer_backward", {3: 0}),
+                     ("sn_soft_weights_forward", {0: 0}), ("sn_soft_weights_forward", {2: 0}),
+                     ("sn_soft_weights_backward", {0: 0}), ("sn_soft_weights_backward", {2: 0}),
+                     ("sn_soft_weights_backward_ordered", {0: 0}), ("sn_soft_weights_backward_ordered", {2: 0}),
+                     ("sn_weighted_gather_forward", {0: 0}), ("sn_weighted_gather_forward", {3: 0}), ("sn_weighted_gather_forward", {1: 0}),
+                     ("sn_weighted_gather_backward", {0: 0}), ("sn_weighted_gather_backward", {3: 0}),
+                     ("sn_weighted_gather_backward_ordered", {0: 0}), ("sn_weighted_gather_backward_ordered", {3: 0}),
+                     ("sn_soft_project_backward", {0: 0}), ("sn_soft_project_backward", {2: 0}),
+                     ("sn_soft_project_backward_ordered", {0: 0}), ("sn_soft_project_backward_ordered", {2: 0}),
+                     ("sn_group_point", {0: 0}), ("sn_group_point", {3: 0}), ("sn_group_point", {4: 0}), ("sn_group_point", {2: 0}),
+                     ("sn_group_point_grad", {0: 0}), ("sn_group_point_grad", {1: 0}), ("sn_group_point_grad", {2: 0}),
+                     ("sn_grouping_operation", {0: 0}), ("sn_grouping_operation", {3: 0}),
+                     ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
+                     ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
+        out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
+    return out
+
+
+CASES = _cases()
+IN_SCOPE = sorted(ENTRIES) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits"]
+
+_CHILD = r"""
+import ctypes, json, sys
+sys.path.insert(0, %r)
+from samplenet_amd._lib import lib
+cases = json.load(sys.stdin)
+host = (ctypes.c_int * 1)(4)
+res = []
+for cid, name, args, _, _ in cases:
+    conv = [ctypes.c_void_p(4096) if a == "PTR" else (ctypes.cast(host, ctypes.c_void_p) if a == "HOSTI" else a) for a in args]
+    rc = getattr(lib, name)(*conv)
+    res.append([cid, int(rc), (lib.sn_last_error_string() or b"").decode()])
+print("RESULTS " + json.dumps(res))
+"""
+
+
+@pytest.fixture(scope="module")
+def results():
+    env = dict(os.environ)
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")  # argument checks need no device: none is offered
+    p = subprocess.run([sys.executable, "-c", _CHILD % ROOT], input=json.dumps(CASES), capture_output=True, text=True, env=env,
+                       timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = [l for l in p.stdout.splitlines() if l.startswith("RESULTS ")][-1]
+    return {cid: (rc, msg) for cid, rc, msg in json.loads(line[len("RESULTS "):])}
+
+
+def test_the_table_walks_every_entry_in_scope():
+    from samplenet_amd import _lib
+
+    for name, (base, sizes, required) in ENTRIES.items():
+        proto = _lib.PROTOTYPES[name]
+        assert len(base) == len(proto), name
+        for pos, ty in enumerate(proto):
+            if pos in sizes:
+                assert ty is ctypes.c_int, (name, pos)
+            if pos in required or base[pos] in (Pp, HOSTI):
+                assert ty is ctypes.c_void_p, (name, pos)
+            if ty is ctypes.c_void_p:
+                assert base[pos] in (Pp, HOSTI, None), (name, pos)
+    assert not [n for n in IN_SCOPE if n not in _lib.PROTOTYPES]
+    assert len({c[0] for c in CASES}) == len(CASES)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_argument_table(results, case):
+    cid, name, args, want, text = case
+    rc, msg = results[cid]
+    assert rc == want, (cid, rc, msg)
+    if text is not None:
+        assert text in msg, (cid, msg)
+        assert msg.startswith(name + ":"), (cid, msg)  # the entry's own name, not that of a shared implementation
+
+
+def test_size_queries():
+    """sn_pairscan_workspace_bytes / sn_soft_bwd_splits are pure host functions: the documented shape of their answers."""
+    from samplenet_amd._lib import lib
+
+    assert lib.sn_pairscan_workspace_bytes(32, 4100, 64) == 0  # the multi-chunk scan takes no scratch
+    assert lib.sn_pairscan_workspace_bytes(1024, 1024, 64) == 0  # the batch alone fills the chip: one workgroup per cloud
+    for B, N, M in ((1, 1, 1), (1, 64, 64), (32, 1024, 64), (17, 2048, 2100), (512, 1024, 64), (513, 1024, 64)):
+        wb = lib.sn_pairscan_workspace_bytes(B, N, M)
+        assert wb >= 0 and wb % 8 == 0 and wb <= 8 * B * N * min(M, 512)
+    assert lib.sn_pairscan_workspace_bytes(32, 1024, 64) == 32 * 16 * 1024 * 8
+    for b, m in ((1, 1), (1, 64), (32, 64), (2048, 64), (1, 5000), (0, 4)):
+        s = lib.sn_soft_bwd_splits(b, m)
+        assert 1 <= s <= max(1, (m + 3) // 4)
+    assert lib.sn_soft_bwd_splits(32, 64) == 16 and lib.sn_soft_bwd_splits(1, 64) == 16 and lib.sn_soft_bwd_splits(2048, 64) == 1
