@@ -7,6 +7,7 @@ is missing -- there is no CPU or eager-PyTorch fallback.
 """
 from . import _lib  # noqa: F401  (loads the HIP library or raises)
 from . import ops, sputils  # noqa: F401
+from .autoencoder import PointNetAE, reconstruction_loss  # noqa: F401
 from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: F401
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
@@ -14,4 +15,4 @@ from .samplers import FPSSampler, RandomSampler  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
-           "progressive_sizes", "sputils", "ops"]
+           "progressive_sizes", "PointNetAE", "reconstruction_loss", "sputils", "ops"]
