@@ -6,7 +6,8 @@ encoders_decoders.py:24-257, samplenet_pointnet_ae.py:57-74, 122-149) on HIP ker
 
 The encoder runs on the kernels of the sampler's own feature extractor (pointnet.py: the one-call conv stack in training mode where
 the shape allows, sn_layer_forward_bn otherwise; sn_linear_forward + sn_bn_eval_coef in eval mode); unlike the sampler's extractor
-it hands a gradient to its INPUT -- the sampler is trained through the frozen autoencoder.  The decoder runs as the sn_skinny_linear
+it hands a gradient to its INPUT -- the sampler is trained through the frozen autoencoder.  Forward and backward are pointnet.py's
+layer-by-layer walk (_conv_stack_fwd, _pool_bwd_bn, _conv_stack_bwd: data gradient only when frozen).  The decoder runs as the sn_skinny_linear
 composition (three launches each way, row blocks of 128); weight gradients of a trainable decoder come from sn_skinny_wgrad.  A
 single-launch decoder was built, lost to the composition and is NOT part of the library (profiles/ae/
 decoder_single_launch_experiment.txt).  There is no CPU route.
@@ -20,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import pointnet
-from ._lib import check, lib, ptr, stream_of
+from ._lib import stream_of
 from .task_features import _skinny, _skinny_wgrad, _trunk_scratch
 
 CONV_STACK = True  # test hook: False = the encoder's training forward layer by layer at every shape
@@ -37,88 +38,36 @@ class _EncoderFunction(torch.autograd.Function):
     def forward(ctx, net, training, x, *params):
         convs = _conv_layers(net)
         B, N, _ = x.shape
-        R = B * N
         C5 = convs[-1].Co
         with torch.cuda.device(x.device):
-            st = stream_of(x)
-            pooled = torch.empty(B, C5, device=x.device, dtype=torch.float32)
-            argsel = torch.empty(B, C5, device=x.device, dtype=torch.int32)
-            zsel = torch.empty(B, C5, device=x.device, dtype=torch.float32)
-            saved = {"zc": [], "cc": []}
-            fuse = (training and CONV_STACK and R > 64 and N % 64 == 0 and C5 % 64 == 0 and convs[-1].Ci % 64 == 0
+            pooled, argsel, zsel = pointnet._pool_bufs(B, C5, x)
+            saved = {"x": x, "B": B, "N": N, "pooled": pooled, "argsel": argsel, "zsel": zsel}
+            fuse = (training and CONV_STACK and B * N > 64 and N % 64 == 0 and C5 % 64 == 0 and convs[-1].Ci % 64 == 0
                     and pointnet._conv_stack_fx(net, convs, x, B, N, saved, pooled, argsel, zsel))
             if not fuse:
-                a_in, coef_prev = x.view(R, 3), None
-                for L in convs:
-                    if training:
-                        z, coef = pointnet._layer_fwd_bn(R, L, a_in, coef_prev)
-                    else:
-                        z, _, _ = pointnet._linear_fwd(R, L, a_in, coef_prev, False)
-                        coef = pointnet._bn_coef(L, R, None, 0, False)
-                    saved["zc"].append(z)
-                    saved["cc"].append(coef)
-                    a_in, coef_prev = z, coef
-                check(lib.sn_pool_forward(B, N, C5, ptr(a_in), ptr(coef_prev), ptr(pooled), ptr(argsel), ptr(zsel), st), "sn_pool_forward")
-            elif saved["zc"][0] is None and any(ctx.needs_input_grad):
-                # The one-call stack did not keep the xyz layer's output (Z1_FREE) and the per-layer backward below reads it: one more
-                # sn_linear_forward launch and an (R, 64) tensor per differentiated training-mode step (nothing when no gradient is
-                # asked).  It is the expression pointnet.backward_impl's own _z1() rebuilds on demand; its rounding may differ in the
-                # last bit from what the stack's kernels formed for their statistics -- inside the fp64 bars of the tests.
-                saved["zc"][0] = pointnet._linear_fwd(R, convs[0], x.view(R, 3), None, False)[0]
+                saved["zc"], saved["cc"] = pointnet._conv_stack_fwd(convs, x, training, (pooled, argsel, zsel))
+            elif any(ctx.needs_input_grad):
+                # the per-layer backward reads the xyz layer's output, which the one-call stack may not have kept: rebuilt here,
+                # in the forward, so that a differentiated step issues its launches in one fixed order (nothing when no gradient is asked)
+                pointnet._z1(convs, saved)
         ctx.net, ctx.training, ctx.saved = net, bool(training), saved
-        ctx.x, ctx.pooled, ctx.argsel, ctx.zsel = x, pooled, argsel, zsel
         return pooled
 
     @staticmethod
     def backward(ctx, g):
-        net, saved, x = ctx.net, ctx.saved, ctx.x
+        net, saved = ctx.net, ctx.saved
         convs = _conv_layers(net)
-        zc, cc = saved["zc"], saved["cc"]
-        B, N, _ = x.shape
-        R = B * N
         fixed = not ctx.training
         trainable = any(ctx.needs_input_grad[3:])
         g = g.contiguous().float()
         grads = {}
-        with torch.cuda.device(x.device):
-            st = stream_of(x)
-            L5 = convs[4]
-            C5 = L5.Co
-            gsel = torch.empty(B, C5, device=x.device, dtype=torch.float32)
-            kcoef = torch.empty(3, C5, device=x.device, dtype=torch.float32)
-            dg, dbt, dbs = torch.empty_like(L5.bn.weight), torch.empty_like(L5.bn.bias), torch.empty_like(L5.b)
-            check(lib.sn_pool_backward_bn(B, C5, -1 if fixed else R, ptr(g), ptr(ctx.pooled), ptr(ctx.zsel), ptr(gsel), ptr(cc[4]), ptr(dg),
-                                          ptr(dbt), ptr(dbs), ptr(kcoef), st), "sn_pool_backward_bn")
-            grads["bn5.weight"], grads["bn5.bias"], grads["conv5.bias"] = dg, dbt, dbs
-            dy = None
-            for i in (4, 3, 2, 1):
-                L, Lp = convs[i], convs[i - 1]
-                mode = pointnet.DZ_POOL if i == 4 else pointnet.DZ_BN
-                gs, ag = (gsel, ctx.argsel) if i == 4 else (None, None)
-                if trainable:
-                    dW, _, dy, dg, dbt, dbs, kcoef = pointnet._layer_bwd(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zc[i - 1], cc[i - 1], Lp, None,
-                                                                         L.name, Lp.bn_name, Lp.name, False, -1 if fixed else 0)
-                    grads[L.name + ".weight"] = dW
-                    grads[Lp.bn_name + ".weight"], grads[Lp.bn_name + ".bias"], grads[Lp.name + ".bias"] = dg, dbt, dbs
-                else:  # frozen: the data gradient alone.  (sn_pool_dgrad_sparse is not used for the top layer: with a BatchNorm its dZ
-                    # is dense in training mode, and in eval mode it would need the per-channel scale folded into g first -- an extra
-                    # elementwise launch for a kernel written for BatchNorm-free stacks; the dense dgrad serves every M.)
-                    dy, stats, nblk = pointnet._dgrad(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zc[i - 1], cc[i - 1])
-                    if fixed:  # running statistics: dZ = scale dY
-                        kcoef = torch.zeros(3, Lp.Co, device=x.device, dtype=torch.float32)
-                        kcoef[0].copy_(cc[i - 1][0])
-                    else:
-                        kcoef = pointnet._bn_bwd(Lp, R, stats, nblk, cc[i - 1])[3]
-            L1 = convs[0]
-            if trainable:
-                grads["conv1.weight"] = pointnet._wgrad(R, L1, pointnet.DZ_BN, dy, zc[0], kcoef, None, None, N, x.view(R, 3), None, False)[0]
-            gx = None
-            if ctx.needs_input_grad[2]:
-                gx = pointnet._dgrad(R, L1, pointnet.DZ_BN, dy, zc[0], kcoef, None, None, N, x.view(R, 3), None)[0].view(B, N, 3)
+        with torch.cuda.device(g.device):
+            gsel, kcoef = pointnet._pool_bwd_bn(convs[-1], saved, g, fixed, None, grads)
+            gx = pointnet._conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, wgrads=trainable, input_grad=ctx.needs_input_grad[2])
         out = [None] * len(_ENC_PARAMS)
         if trainable:
             out = [grads[n] if ctx.needs_input_grad[3 + j] else None for j, n in enumerate(_ENC_PARAMS)]
-        return (None, None, gx) + tuple(out)
+        return (None, None, None if gx is None else gx.view(saved["x"].shape)) + tuple(out)
 
 
 _ENC_PARAMS = tuple("conv%d.%s" % (i, k) for i in range(1, 6) for k in ("weight", "bias")) + \

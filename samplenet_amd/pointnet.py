@@ -5,7 +5,12 @@ Replaces the torch.nn call chain of registration/src/samplenet.py:90-104
     5 x relu(bn(conv1d_k1(.)))  ->  max over points  ->  3 x relu(bn(linear(.)))  ->  linear
 while the parameters stay ordinary nn.Conv1d / nn.BatchNorm1d / nn.Linear members of the module
 (state_dict compatibility).  Host side: buffer allocation and launch sequencing only.
+
+The layer-by-layer walk of a conv stack (_conv_stack_fwd / _pool_bwd_bn / _conv_stack_bwd) lives here once: this head, the
+synchronised-statistics mode (syncbn.py) and the autoencoder's encoder (autoencoder.py) all drive it.
 """
+import ctypes
+
 import torch
 
 from ._lib import check, lib, ptr, stream_of
@@ -20,6 +25,16 @@ def _st(t):
 
 def _empty(shape, like, dtype=torch.float32):
     return torch.empty(shape, device=like.device, dtype=dtype)
+
+
+def _arr(ts):
+    """void* array of the tensors' device pointers (None -> NULL)."""
+    return (ctypes.c_void_p * len(ts))(*[ptr(t) for t in ts])
+
+
+def _pool_bufs(B, C, like):
+    """(pooled, argsel, zsel) of the max-pool over the points: values, selected point per channel, pre-BatchNorm value there."""
+    return _empty((B, C), like), _empty((B, C), like, torch.int32), _empty((B, C), like)
 
 
 class _Layer:
@@ -148,37 +163,35 @@ def _momentum(bn):
     return 1.0 / (float(bn.num_batches_tracked.item()) + 1.0)  # (host read: not capturable; momentum=None is rare)
 
 
+def _bn_args(bn, update, momentum=None):
+    """The BatchNorm argument run of the forward entry points: weight, bias, eps, momentum, running_mean, running_var,
+    num_batches_tracked (the last three NULL unless `update`: no running-statistics update).  momentum: a fixed factor in place
+    of _momentum(bn)."""
+    run = (ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)) if update else (None, None, None)
+    return (ptr(bn.weight), ptr(bn.bias), float(bn.eps), _momentum(bn) if momentum is None else momentum) + run
+
+
 def _layer_fwd_bn(R, L, a_in, coef_prev):
     """Training forward of a layer with BatchNorm: pre-BN output z and coef (scale, shift, mean, invstd); running
     statistics updated in place.  One launch when R <= 32 (finalisation fused), GEMM + bn_finalize otherwise."""
-    bn = L.bn
     z = _empty((R, L.Co), a_in)
     coef = _empty((4, L.Co), a_in)
     stats = _empty((lib.sn_linear_stats_blocks(R), 2, L.Co), a_in)
-    mom = _momentum(bn)
-    upd = bn.track_running_stats
     check(lib.sn_layer_forward_bn(R, L.Ci, L.Co, ptr(a_in), ptr(coef_prev), ptr(L.W), ptr(L.b), ptr(z), ptr(stats),
-                                  ptr(bn.weight), ptr(bn.bias), float(bn.eps), float(mom),
-                                  ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-                                  ptr(bn.num_batches_tracked) if upd else None, ptr(coef), _st(a_in)), "sn_layer_forward_bn")
+                                  *_bn_args(L.bn, L.bn.track_running_stats), ptr(coef), _st(a_in)), "sn_layer_forward_bn")
     return z, coef
 
 
 def _layer_fwd_bn_pool(R, npts, L, a_in, coef_prev, pooled, argsel, zsel):
     """_layer_fwd_bn of the last conv layer + the max-pool over the points (sn_conv_forward_bn_pool)."""
-    bn = L.bn
     z = _empty((R, L.Co), a_in)
     coef = _empty((4, L.Co), a_in)
     nblk = lib.sn_linear_stats_blocks(R)
     stats = _empty((nblk, 2, L.Co), a_in)
     pool_val = _empty((nblk, 2, L.Co), a_in)
     pool_idx = _empty((nblk, 2, L.Co), a_in, torch.int32)
-    mom = _momentum(bn)
-    upd = bn.track_running_stats
     check(lib.sn_conv_forward_bn_pool(R, L.Ci, L.Co, npts, ptr(a_in), ptr(coef_prev), ptr(L.W), ptr(L.b), ptr(z), ptr(stats),
-                                      ptr(bn.weight), ptr(bn.bias), float(bn.eps), float(mom),
-                                      ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-                                      ptr(bn.num_batches_tracked) if upd else None, ptr(coef), ptr(pool_val), ptr(pool_idx),
+                                      *_bn_args(L.bn, L.bn.track_running_stats), ptr(coef), ptr(pool_val), ptr(pool_idx),
                                       ptr(pooled), ptr(argsel), ptr(zsel), _st(a_in)), "sn_conv_forward_bn_pool")
     return z, coef
 
@@ -188,15 +201,41 @@ def _bn_coef(L, R, stats, nblk, training):
     C = L.Co
     coef = _empty((4, C), L.W)
     if training or not bn.track_running_stats:
-        mom = _momentum(bn)
-        upd = training and bn.track_running_stats
-        check(lib.sn_bn_finalize(nblk, C, R, ptr(stats), ptr(bn.weight), ptr(bn.bias), float(bn.eps), float(mom),
-                                 ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-                                 ptr(bn.num_batches_tracked) if upd else None, ptr(coef), _st(L.W)), "sn_bn_finalize")
+        check(lib.sn_bn_finalize(nblk, C, R, ptr(stats), *_bn_args(bn, training and bn.track_running_stats), ptr(coef), _st(L.W)),
+              "sn_bn_finalize")
     else:
         check(lib.sn_bn_eval_coef(C, ptr(bn.weight), ptr(bn.bias), float(bn.eps), ptr(bn.running_mean), ptr(bn.running_var),
                                   ptr(coef), _st(L.W)), "sn_bn_eval_coef")
     return coef
+
+
+def _conv_stack_fwd(convs, x_bnc, training, pool, fuse_pool=False, coef_fn=None):
+    """conv1..convN layer by layer on the (B*N, 3) rows of the cloud, then the max-pool into pool = (pooled, argsel, zsel)
+    -> (pre-BatchNorm outputs z, coefficient blocks), one per layer.  The per-layer step: training = batch statistics
+    (_layer_fwd_bn; fuse_pool: the last layer's launch also pools), otherwise running statistics; coef_fn(L, R, stats, nblk) ->
+    coef: the GEMM with statistics partials, then the caller's own coefficients (syncbn: statistics of all ranks)."""
+    B, N, _ = x_bnc.shape
+    R = B * N
+    a_in, coef = x_bnc.view(R, 3), None
+    zs, cs = [], []
+    for L in convs:
+        if coef_fn is not None:
+            z, stats, nblk = _linear_fwd(R, L, a_in, coef, True)
+            coef = coef_fn(L, R, stats, nblk)
+        elif training and fuse_pool and L is convs[-1]:
+            z, coef = _layer_fwd_bn_pool(R, N, L, a_in, coef, *pool)
+        elif training:
+            z, coef = _layer_fwd_bn(R, L, a_in, coef)
+        else:
+            z, stats, nblk = _linear_fwd(R, L, a_in, coef, False)
+            coef = _bn_coef(L, R, stats, nblk, False)
+        zs.append(z)
+        cs.append(coef)
+        a_in = z
+    if not fuse_pool:
+        check(lib.sn_pool_forward(B, N, convs[-1].Co, ptr(a_in), ptr(coef), ptr(pool[0]), ptr(pool[1]), ptr(pool[2]), _st(x_bnc)),
+              "sn_pool_forward")
+    return zs, cs
 
 
 def _conv_stack_fx(net, convs, x_bnc, B, N, saved, pooled, argsel, zsel, defer_pool=False, rec=None):
@@ -205,8 +244,6 @@ def _conv_stack_fx(net, convs, x_bnc, B, N, saved, pooled, argsel, zsel, defer_p
     saved["cc"]; returns False when the shapes are not supported (the per-layer path runs instead).
     defer_pool: stop after the last GEMM -- the last BatchNorm and the pool pick run as the first stage of the FC chain
     (_fc_chain_fwd with saved["pool_tail"])."""
-    import ctypes
-
     n = len(convs)
     chans = (ctypes.c_int * (n + 1))(convs[0].Ci, *[L.Co for L in convs])
     if any(L.bn.momentum is None or not L.bn.track_running_stats for L in convs):
@@ -232,17 +269,12 @@ def _conv_stack_fx(net, convs, x_bnc, B, N, saved, pooled, argsel, zsel, defer_p
     # (defer_pool: the last layer leaves (B, 2, Cn) 64-bit keys here instead of the block partials)
     pool_val = _empty((max(nblk, 2 * B) if defer_pool else nblk, 2, Cn), x_bnc)
     pool_idx = _empty((nblk, 2, Cn), x_bnc, torch.int32)
-    VP = ctypes.c_void_p * n
-
-    def arr(ts):
-        return VP(*[ptr(t) for t in ts])
-
     eps = (ctypes.c_float * n)(*[float(L.bn.eps) for L in convs])
     mom = (ctypes.c_float * n)(*[float(L.bn.momentum) for L in convs])
-    args = [B, N, n, chans, ptr(x_bnc), arr([L.W for L in convs]), arr([L.b for L in convs]),
-            arr([L.bn.weight for L in convs]), arr([L.bn.bias for L in convs]),
-            arr([L.bn.running_mean for L in convs]), arr([L.bn.running_var for L in convs]),
-            arr([L.bn.num_batches_tracked for L in convs]), eps, mom, arr(zs), arr(cs), ptr(acc),
+    args = [B, N, n, chans, ptr(x_bnc), _arr([L.W for L in convs]), _arr([L.b for L in convs]),
+            _arr([L.bn.weight for L in convs]), _arr([L.bn.bias for L in convs]),
+            _arr([L.bn.running_mean for L in convs]), _arr([L.bn.running_var for L in convs]),
+            _arr([L.bn.num_batches_tracked for L in convs]), eps, mom, _arr(zs), _arr(cs), ptr(acc),
             ptr(pool_val), ptr(pool_idx), *([None] * 3 if defer_pool else [ptr(pooled), ptr(argsel), ptr(zsel)]), _st(x_bnc)]
     try:
         check(lib.sn_conv_stack_forward_bn(*args), "sn_conv_stack_forward_bn")
@@ -277,8 +309,6 @@ def _fc_chain_fwd(net, hidden, pooled, B, saved, rec=None, out=None):
     out = (last FC layer, out_bn record): the classification sampler's output layer + BatchNorm as the chain's last stage
     (sn_fc_chain_forward_pool_out) where the shape allows -- saved["y_out"] then holds the head's output and saved["z_out"] /
     saved["c_out"] what backward_impl needs; otherwise the caller runs _last_layer."""
-    import ctypes
-
     shape = _fc_chain_shape(hidden, B)
     if shape is None:
         return False
@@ -290,17 +320,12 @@ def _fc_chain_fwd(net, hidden, pooled, B, saved, rec=None, out=None):
     xbuf = _empty((2 * 32 * H,), pooled)
     zs = [_empty((B, H), pooled) for _ in hidden]
     cs = [_empty((4, H), pooled) for _ in hidden]
-    VP = ctypes.c_void_p * n
-
-    def arr(ts):
-        return VP(*[ptr(t) for t in ts])
-
     eps = (ctypes.c_float * n)(*[float(L.bn.eps) for L in hidden])
     mom = (ctypes.c_float * n)(*[float(L.bn.momentum) for L in hidden])
-    layer_args = (arr([L.W for L in hidden]), arr([L.b for L in hidden]),
-                  arr([L.bn.weight for L in hidden]), arr([L.bn.bias for L in hidden]),
-                  arr([L.bn.running_mean for L in hidden]), arr([L.bn.running_var for L in hidden]),
-                  arr([L.bn.num_batches_tracked for L in hidden]), eps, mom, arr(zs), arr(cs), ptr(xbuf), ptr(sync), _st(pooled))
+    layer_args = (_arr([L.W for L in hidden]), _arr([L.b for L in hidden]),
+                  _arr([L.bn.weight for L in hidden]), _arr([L.bn.bias for L in hidden]),
+                  _arr([L.bn.running_mean for L in hidden]), _arr([L.bn.running_var for L in hidden]),
+                  _arr([L.bn.num_batches_tracked for L in hidden]), eps, mom, _arr(zs), _arr(cs), ptr(xbuf), ptr(sync), _st(pooled))
     tail = saved.pop("pool_tail", None)
     if tail is not None:
         acc, pool_val, pool_idx, L5, nconv, N, argsel, zsel = tail
@@ -394,33 +419,17 @@ def forward_impl(net, x_bnc, training, skip_last=False, use_plan=True):
         if not capturing:  # (a plan's buffers must not come from a graph's private pool)
             rec = []
     saved = {"x": x_bnc, "B": B, "N": N, "zc": [], "cc": [], "zf": [], "cf": [], "training": bool(training)}
-    use_batch_stats = training
-    a_in, coef_prev = x_bnc.view(R, 3), None
     C5 = convs[-1].Co
-    pooled = _empty((B, C5), x_bnc)
-    argsel = _empty((B, C5), x_bnc, torch.int32)
-    zsel = _empty((B, C5), x_bnc)
+    pooled, argsel, zsel = _pool_bufs(B, C5, x_bnc)
     # last conv layer: the max-pool is folded into its epilogue + BatchNorm finalisation when the shapes are 64-aligned
     fuse_pool = training and R > 64 and N % 64 == 0 and C5 % 64 == 0 and convs[-1].Ci % 64 == 0 and FUSE_POOL
     # ... and its BatchNorm finalisation + pool pick into the FC chain when that one runs (B <= 32, the 128 -> 256 x 3 head)
     shape = _fc_chain_shape(fcs[:-1], B) if training and FC_CHAIN and POOL_IN_CHAIN else None
     defer_pool = shape is not None and bool(lib.sn_fc_chain_forward_pool_supported(B, N, *shape))
-    if fuse_pool and FX_STATS and _conv_stack_fx(net, convs, x_bnc, B, N, saved, pooled, argsel, zsel, defer_pool, rec):
-        convs = []  # the whole stack ran as one call (fixed-point statistics chain)
-    for li, L in enumerate(convs):
-        if training and fuse_pool and li == len(convs) - 1:
-            z, coef = _layer_fwd_bn_pool(R, N, L, a_in, coef_prev, pooled, argsel, zsel)
-        elif training:
-            z, coef = _layer_fwd_bn(R, L, a_in, coef_prev)
-        else:
-            z, stats, nblk = _linear_fwd(R, L, a_in, coef_prev, use_batch_stats)
-            coef = _bn_coef(L, R, stats, nblk, training)
-        saved["zc"].append(z)
-        saved["cc"].append(coef)
-        a_in, coef_prev = z, coef
-    if not fuse_pool:
-        check(lib.sn_pool_forward(B, N, C5, ptr(a_in), ptr(coef_prev), ptr(pooled), ptr(argsel), ptr(zsel), _st(x_bnc)),
-              "sn_pool_forward")
+    # the whole stack as one call (fixed-point statistics chain), else layer by layer
+    fx = fuse_pool and FX_STATS and _conv_stack_fx(net, convs, x_bnc, B, N, saved, pooled, argsel, zsel, defer_pool, rec)
+    if not fx:
+        saved["zc"], saved["cc"] = _conv_stack_fwd(convs, x_bnc, training, (pooled, argsel, zsel), fuse_pool)
     saved.update(pooled=pooled, argsel=argsel, zsel=zsel)
     a_in, coef_prev = pooled, None
     hidden = fcs[:-1]
@@ -438,23 +447,20 @@ def forward_impl(net, x_bnc, training, skip_last=False, use_plan=True):
             # workgroup, and sum / sum-of-squares partials lose digits on the head's nearly-constant features)
             z, _, _ = _linear_fwd(B, L, a_in, coef_prev, False, fc_rows=True)
             coef = _empty((4, L.Co), z)
-            bn, upd = L.bn, L.bn.track_running_stats
-            check(lib.sn_bn_batch_stats_twopass(B, L.Co, ptr(z), ptr(bn.weight), ptr(bn.bias), float(bn.eps), _momentum(bn),
-                                                ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-                                                ptr(bn.num_batches_tracked) if upd else None, ptr(coef), _st(z)),
+            check(lib.sn_bn_batch_stats_twopass(B, L.Co, ptr(z), *_bn_args(L.bn, L.bn.track_running_stats), ptr(coef), _st(z)),
                   "sn_bn_batch_stats_twopass")
         elif training:
             z, coef = _layer_fwd_bn(B, L, a_in, coef_prev)
         else:
-            z, stats, nblk = _linear_fwd(B, L, a_in, coef_prev, use_batch_stats)
-            coef = _bn_coef(L, B, stats, nblk, training)
+            z, stats, nblk = _linear_fwd(B, L, a_in, coef_prev, False)
+            coef = _bn_coef(L, B, stats, nblk, False)
         saved["zf"].append(z)
         saved["cf"].append(coef)
         a_in, coef_prev = z, coef
     y = saved.get("y_out")  # (the chain's output stage produced the head's output already)
     if y is None and (ob is not None or not skip_last):  # (an output BatchNorm needs every cloud's row: the caller cannot produce y itself)
         y = _last_layer(B, fcs[-1], ob, a_in, coef_prev, training, saved)
-    if rec is not None and len(rec) == 2 and not convs and not hidden:
+    if rec is not None and len(rec) == 2 and fx and not hidden:
         # the whole head ran as the two fused calls (+ the last layer): from now on steps of this shape replay them
         _ForwardPlan.register(net, x_bnc, skip_last, rec, saved, (fcs[-1], ob))
     return y, saved
@@ -471,18 +477,16 @@ def _last_layer(B, L, ob, a_in, coef_prev, training, saved):
     upd = bool(training and bn.track_running_stats)
     coef = _empty((4, L.Co), a_in)
     y = _empty((B, L.Co), a_in)
-    rm, rv, nbt = (ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)) if upd else (None, None, None)
     if batch_stats and B <= 32 and L.Ci in (64, 128, 256, 512):
         z = _empty((B, L.Co), a_in)
-        check(lib.sn_layer_forward_bn_out(B, L.Ci, L.Co, ptr(a_in), ptr(coef_prev), ptr(L.W), ptr(L.b), ptr(z), ptr(bn.weight),
-                                          ptr(bn.bias), float(bn.eps), _momentum(bn), rm, rv, nbt, ptr(coef), ptr(y), _st(a_in)),
-              "sn_layer_forward_bn_out")
+        check(lib.sn_layer_forward_bn_out(B, L.Ci, L.Co, ptr(a_in), ptr(coef_prev), ptr(L.W), ptr(L.b), ptr(z), *_bn_args(bn, upd),
+                                          ptr(coef), ptr(y), _st(a_in)), "sn_layer_forward_bn_out")
     else:
         z = _linear_fwd(B, L, a_in, coef_prev, False, fc_rows=True)[0]
-        if not batch_stats:
-            rm, rv = ptr(bn.running_mean), ptr(bn.running_var)
-        check(lib.sn_bn_output_forward(B, L.Co, 1 if batch_stats else 0, ptr(z), ptr(bn.weight), ptr(bn.bias), float(bn.eps),
-                                       _momentum(bn) if batch_stats else 0.0, rm, rv, nbt, ptr(coef), ptr(y), _st(a_in)),
+        bn_args = _bn_args(bn, upd, None if batch_stats else 0.0)
+        if not batch_stats:  # the running statistics as INPUT (applied, not updated)
+            bn_args = bn_args[:4] + (ptr(bn.running_mean), ptr(bn.running_var), None)
+        check(lib.sn_bn_output_forward(B, L.Co, 1 if batch_stats else 0, ptr(z), *bn_args, ptr(coef), ptr(y), _st(a_in)),
               "sn_bn_output_forward")
     saved["z_out"], saved["c_out"], saved["out_fixed"] = z, coef, not batch_stats
     return y
@@ -699,21 +703,28 @@ def _wgrad(R, L, mode, dy, z, kcoef, gsel, argsel, npts, aprev, coef_prev, with_
     return dW, db
 
 
-def _dgrad(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev):
+def _stats_blocks(nblk, C, like, zero):
+    """(sum dY, sum dY Z) partials of the BatchNorm below for a backward kernel to fill.  zero: which of the blocks a kernel variant
+    fills depends on the route the shape takes inside the library (one per 64-row tile, or one per workgroup of the fused
+    kernels); a caller that sums over all of them itself (syncbn) must not see what the kernel left unwritten."""
+    return (torch.zeros if zero else torch.empty)((nblk, 2, C), device=like.device, dtype=torch.float32)
+
+
+def _dgrad(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, zero_stats=False):
     dyprev = _empty((R, L.Ci), L.W)
     nblk = lib.sn_linear_stats_blocks(R)
-    stats = _empty((nblk, 2, L.Ci), L.W) if coef_prev is not None else None
+    stats = _stats_blocks(nblk, L.Ci, L.W, zero_stats) if coef_prev is not None else None
     check(lib.sn_linear_dgrad(R, L.Ci, L.Co, mode, ptr(dy), ptr(z), ptr(kcoef), ptr(gsel), ptr(argsel), npts, ptr(L.W),
                               ptr(zprev), ptr(coef_prev), ptr(dyprev), ptr(stats), _st(L.W)), "sn_linear_dgrad")
     return dyprev, stats, nblk
 
 
-def _bwd_layer(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, sink=None, name=""):
-    """dgrad + wgrad of one layer through sn_linear_backward (one launch on the fast path)."""
-    dW = _out(sink, name + ".weight", L.W)
+def _linear_bwd(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, sink=None, zero_stats=False):
+    """dgrad + wgrad of one layer through sn_linear_backward; the BatchNorm below is left to the caller (its sums: stats)."""
+    dW = _out(sink, L.name + ".weight", L.W)
     dyprev = _empty((R, L.Ci), L.W)
     nblk = lib.sn_linear_stats_blocks(R)
-    stats = _empty((nblk, 2, L.Ci), L.W)
+    stats = _stats_blocks(nblk, L.Ci, L.W, zero_stats)
     nsplit = lib.sn_linear_wgrad_splits(R, L.Ci, L.Co, 0)
     part = _empty((nsplit * L.Co * L.Ci,), L.W)
     check(lib.sn_linear_backward(R, L.Ci, L.Co, mode, ptr(dy), ptr(z), ptr(kcoef), ptr(gsel), ptr(argsel), npts, ptr(L.W),
@@ -758,11 +769,95 @@ def _layer_bwd(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, L
     return dW, db, dyprev, dg, dbt, dbs, kc
 
 
+def _z1(convs, saved):
+    """The xyz layer's pre-BatchNorm output for the per-layer backward, rebuilt from the cloud when the one-call forward did not
+    keep it (Z1_FREE: saved["zc"][0] is None).  One sn_linear_forward launch; its rounding may differ in the last bit from what
+    the stack's kernels formed for their statistics."""
+    zc, x = saved["zc"], saved["x"]
+    if zc[0] is None:
+        zc[0] = _linear_fwd(x.shape[0] * x.shape[1], convs[0], x.view(-1, convs[0].Ci), None, False)[0]
+    return zc[0]
+
+
+def _pool_bwd_bn(L, saved, g_pool, fixed, sink, grads):
+    """Max-pool backward + the BatchNorm backward of the last conv layer L in a launch of their own: g_pool (B, C), the gradient
+    w.r.t. the pooled features -> (gsel, kcoef) for _conv_stack_bwd; L's BatchNorm / bias gradients into grads."""
+    B, C = g_pool.shape
+    gsel = _empty((B, C), g_pool)
+    dgamma, dbeta = _out(sink, L.bn_name + ".weight", L.bn.weight), _out(sink, L.bn_name + ".bias", L.bn.bias)
+    dbias = _out(sink, L.name + ".bias", L.b)
+    kcoef = _empty((3, C), g_pool)
+    check(lib.sn_pool_backward_bn(B, C, -1 if fixed else B * saved["N"], ptr(g_pool), ptr(saved["pooled"]), ptr(saved["zsel"]),
+                                  ptr(gsel), ptr(saved["cc"][-1]), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(kcoef), _st(g_pool)),
+          "sn_pool_backward_bn")
+    grads[L.bn_name + ".weight"], grads[L.bn_name + ".bias"], grads[L.name + ".bias"] = dgamma, dbeta, dbias
+    return gsel, kcoef
+
+
+def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=True, input_grad=False, bn_bwd=None, in3=False):
+    """The conv stack's backward layer by layer, convN -> conv1, from gsel (B, C): the gradient at the max-pooled points, and
+    kcoef: the dZ coefficients of convN's BatchNorm.  Fills grads (written into sink where it has the name); returns the gradient
+    w.r.t. the cloud (R, 3) when input_grad, else None.
+    fixed: the forward ran on running statistics -- every BatchNorm backward is dZ = scale * dY (the kernels take "rows < 0").
+    How layer i finishes the BatchNorm of layer i - 1:
+      wgrads, no bn_bwd   inside its own fused launch (sn_layer_backward);
+      not wgrads          a frozen stack, data gradient only (the dense sn_linear_dgrad serves the pooled top layer too: with a
+                          BatchNorm its dZ is dense): sn_bn_backward_coef on the local sums, scale only when fixed;
+      bn_bwd(i - 1, stats) -> kcoef   the caller's own, from ZEROED block partials behind sn_linear_backward (syncbn).
+    in3 (head only): conv2's fused backward yields conv1's weight gradient in closed form where the library supports the shape."""
+    B, N = saved["B"], saved["N"]
+    R = B * N
+    zc, cc, x_rows = saved["zc"], saved["cc"], saved["x"].view(R, convs[0].Ci)
+    top = len(convs) - 1
+    in3_floats = lib.sn_layer_backward_in3_stats_floats(R, convs[1].Ci, convs[1].Co) if (in3 and convs[0].Ci == 3 and not fixed) else 0
+    dy = None
+    for i in range(top, 0, -1):
+        L, Lp = convs[i], convs[i - 1]
+        if i == 1 and in3_floats > 0:
+            # conv2 sits on the xyz input layer: its fused backward also yields conv1's weight gradient (closed form from
+            # three extra per-channel sums + the moments of x: no pass of its own over dY1)
+            dW = _out(sink, L.name + ".weight", L.W)
+            dW0 = _out(sink, Lp.name + ".weight", Lp.W)
+            dg, dbt = _out(sink, Lp.bn_name + ".weight", Lp.bn.weight), _out(sink, Lp.bn_name + ".bias", Lp.bn.bias)
+            dbs = _out(sink, Lp.name + ".bias", Lp.b)
+            stats = _empty((in3_floats,), L.W)
+            part = _empty((lib.sn_linear_wgrad_splits(R, L.Ci, L.Co, 0) * L.Co * L.Ci,), L.W)
+            kc = _empty((3, L.Ci), L.W)
+            check(lib.sn_layer_backward_in3(R, L.Ci, L.Co, ptr(dy), ptr(zc[1]), ptr(kcoef), ptr(L.W), ptr(_z1(convs, saved)), ptr(cc[0]),
+                                            ptr(stats), ptr(part), ptr(dW), ptr(dg), ptr(dbt), ptr(dbs), ptr(kc),
+                                            ptr(saved["x"]), ptr(Lp.W), ptr(Lp.b), ptr(dW0), _st(L.W)), "sn_layer_backward_in3")
+            grads[L.name + ".weight"], grads[Lp.name + ".weight"] = dW, dW0
+            grads[Lp.bn_name + ".weight"], grads[Lp.bn_name + ".bias"], grads[Lp.name + ".bias"] = dg, dbt, dbs
+            return None
+        # the top layer reads its dZ through the pool's selection, the others apply their BatchNorm's dZ coefficients
+        mode, gs, ag = (DZ_POOL, gsel, saved["argsel"]) if i == top else (DZ_BN, None, None)
+        zprev = zc[i - 1] if i > 1 else _z1(convs, saved)
+        if wgrads and bn_bwd is None:
+            dW, _, dy, dg, dbt, dbs, kcoef = _layer_bwd(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zprev, cc[i - 1], Lp, sink, L.name,
+                                                        Lp.bn_name, Lp.name, False, -1 if fixed else 0)
+            grads[L.name + ".weight"] = dW
+            grads[Lp.bn_name + ".weight"], grads[Lp.bn_name + ".bias"], grads[Lp.name + ".bias"] = dg, dbt, dbs
+        elif wgrads:
+            grads[L.name + ".weight"], dy, stats, _ = _linear_bwd(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zprev, cc[i - 1], sink, True)
+            kcoef = bn_bwd(i - 1, stats)
+        else:
+            dy, stats, nblk = _dgrad(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zprev, cc[i - 1])
+            if fixed:
+                kcoef = torch.zeros(3, Lp.Co, device=dy.device, dtype=torch.float32)
+                kcoef[0].copy_(cc[i - 1][0])
+            else:
+                kcoef = _bn_bwd(Lp, R, stats, nblk, cc[i - 1])[3]
+    L1 = convs[0]
+    if wgrads:
+        grads[L1.name + ".weight"] = _wgrad(R, L1, DZ_BN, dy, _z1(convs, saved), kcoef, None, None, N, x_rows, None, False, sink, L1.name)[0]
+    if input_grad:
+        return _dgrad(R, L1, DZ_BN, dy, _z1(convs, saved), kcoef, None, None, N, x_rows, None)[0]
+    return None
+
+
 def conv_stack_backward_supported(net, B, N):
     """True when backward_impl will run the conv stack through sn_conv_stack_backward (whose closing kernel can carry the
     loss side's deferred tail, fused_step.py)."""
-    import ctypes
-
     if not (FX_STATS and IN3_CLOSED_FORM):
         return False
     convs, _ = _layers(net)
@@ -774,16 +869,9 @@ def _conv_stack_bwd_fx(net, convs, saved, gsel, kcoef_top, sink, grads, names_c,
     """Backward of the conv stack as one call (sn_conv_stack_backward: 5 launches, BatchNorm-backward sums as fixed-point
     atomics, every weight-gradient partial reduced by the closing kernel).  Returns False when the shapes are not
     supported (the per-layer path runs instead)."""
-    import ctypes
-
     n = len(convs)
     B, N = saved["B"], saved["N"]
     x = saved["x"]
-    VP = ctypes.c_void_p * n
-
-    def arr(ts):
-        return VP(*[ptr(t) for t in ts])
-
     # what does not change from step to step when the forward ran on a plan's buffers (saved["_bwd_cache"], shared by the
     # steps of that plan): shape arrays, scratch, the pointer arrays of the weights and of the saved activations
     cache = saved.get("_bwd_cache")
@@ -799,7 +887,7 @@ def _conv_stack_bwd_fx(net, convs, saved, gsel, kcoef_top, sink, grads, names_c,
             acc = torch.zeros(nacc, device=x.device, dtype=torch.int64)  # persistent: every call leaves it zero
             net._fx_acc_b = acc
         scratch = _empty((nscr,), x)
-        st = (chans, acc, scratch, arr([L.W for L in convs]), arr(saved["zc"]), arr(saved["cc"]))
+        st = (chans, acc, scratch, _arr([L.W for L in convs]), _arr(saved["zc"]), _arr(saved["cc"]))
         if cache is not None:
             cache["conv"] = st
     chans, acc, scratch, W_arr, zc_arr, cc_arr = st
@@ -810,7 +898,7 @@ def _conv_stack_bwd_fx(net, convs, saved, gsel, kcoef_top, sink, grads, names_c,
     try:
         check(lib.sn_conv_stack_backward(B, N, n, chans, ptr(x), W_arr, ptr(convs[0].b), zc_arr, cc_arr, ptr(gsel),
                                          ptr(saved["argsel"]), ptr(kcoef_top), ptr(acc), ptr(scratch),
-                                         arr(dW), arr(dg + [None]), arr(dbt + [None]), arr(dbs + [None]), step_tail, _st(x)),
+                                         _arr(dW), _arr(dg + [None]), _arr(dbt + [None]), _arr(dbs + [None]), step_tail, _st(x)),
               "sn_conv_stack_backward")
     except Exception:
         acc.zero_()
@@ -826,19 +914,12 @@ def _fc_chain_bwd(net, convs, fcs, saved, grad_y, sink, grads, fixed, obn=None):
     """The FC head's backward as one launch (sn_fc_chain_backward).  Fills `grads` for every FC parameter and for the last
     conv layer's BatchNorm / bias; returns (gsel, kcoef_top) for the conv stack's backward, or False when the shape is not
     supported (the per-layer launches run instead)."""
-    import ctypes
-
     nf = len(fcs)
     B, R = saved["B"], saved["B"] * saved["N"]
     zf, cf, cc = saved["zf"], saved["cf"], saved["cc"]
     like = grad_y
     L5 = convs[-1]
     C5 = L5.Co
-    VP = ctypes.c_void_p * nf
-
-    def arr(ts):
-        return VP(*[ptr(t) for t in ts])
-
     cache = saved.get("_bwd_cache")
     st = cache.get(("fc", fixed)) if cache is not None else None
     if st is None:
@@ -884,15 +965,15 @@ def _fc_chain_bwd(net, convs, fcs, saved, grad_y, sink, grads, fixed, obn=None):
     grads[fcs[-1].name + ".bias"] = db_top
     ins = st.get("ins")
     if ins is None:  # (pointer arrays of the operands: static with the plan's buffers)
-        ins = (arr(W), arr(zprev), arr(coefprev), (ctypes.c_longlong * nf)(*rows), arr(aprev), (ctypes.c_int * nf)(*araw))
+        ins = (_arr(W), _arr(zprev), _arr(coefprev), (ctypes.c_longlong * nf)(*rows), _arr(aprev), (ctypes.c_int * nf)(*araw))
         st["ins"] = ins
     if obn is not None:  # the output BatchNorm's backward opens the launch (obn: z, coef, fixed, dgamma, dbeta)
         check(lib.sn_fc_chain_backward_obn(B, nf, Co, Ci, ptr(grad_y), ptr(obn[0]), ptr(obn[1]), int(obn[2]), ptr(obn[3]), ptr(obn[4]),
-                                           ins[0], ins[1], ins[2], ins[3], arr(dg), arr(dbt), arr(dbs), arr(dW), ptr(db_top), ins[4],
+                                           ins[0], ins[1], ins[2], ins[3], _arr(dg), _arr(dbt), _arr(dbs), _arr(dW), ptr(db_top), ins[4],
                                            ins[5], ptr(gsel), ptr(kcoef), ptr(xbuf), ptr(sync), _st(like)), "sn_fc_chain_backward_obn")
     else:
         check(lib.sn_fc_chain_backward(B, nf, Co, Ci, ptr(grad_y), ins[0], ins[1], ins[2], ins[3],
-                                       arr(dg), arr(dbt), arr(dbs), arr(dW), ptr(db_top), ins[4], ins[5],
+                                       _arr(dg), _arr(dbt), _arr(dbs), _arr(dW), ptr(db_top), ins[4], ins[5],
                                        ptr(gsel), ptr(kcoef), ptr(xbuf), ptr(sync), _st(like)), "sn_fc_chain_backward")
     saved["fc_chain_b"] = (xbuf, keep)  # (scratch of the asynchronous launch)
     return gsel, kcoef
@@ -910,13 +991,8 @@ def backward_impl(net, saved, grad_y, sink=None, after_fc=None, step_tail=None):
     R = B * N
     grads = {}
     grad_y = grad_y.contiguous()
-    zf, cf, zc, cc = saved["zf"], saved["cf"], saved["zc"], saved["cc"]
-
-    def _z1():
-        # the xyz layer's pre-BatchNorm output for the per-layer backward when the forward did not keep it (Z1_FREE)
-        if zc[0] is None:
-            zc[0] = _linear_fwd(R, convs[0], saved["x"].view(R, 3), None, False)[0]
-        return zc[0]
+    zf, cf, cc = saved["zf"], saved["cf"], saved["cc"]
+    L5 = convs[-1]  # (the last conv layer: the one the max-pool sits on)
 
     # eval-mode forward (running statistics): every BatchNorm backward is dZ = scale * dY -- the kernels take "rows < 0" for
     # that (no batch-statistics terms); the fixed-point / closed-form fast paths assume batch statistics and are skipped
@@ -953,7 +1029,7 @@ def backward_impl(net, saved, grad_y, sink=None, after_fc=None, step_tail=None):
         else:
             # fc1 sits on the max-pool: its "previous layer" is conv5 seen through the selected points -- the ReLU mask and
             # BatchNorm-backward sums of the dgrad epilogue over zsel ARE the pooling backward (no separate launch)
-            zprev, cprev, Lprev, bnp, linp, rows = saved["zsel"], cc[4], convs[4], bn_c[4], names_c[4], (-1 if fixed else R)
+            zprev, cprev, Lprev, bnp, linp, rows = saved["zsel"], cc[-1], L5, L5.bn_name, L5.name, (-1 if fixed else R)
         dW, db, dy, dg, dbt, dbs, kc = _layer_bwd(B, L, mode, dy, zf[j] if j < nf - 1 else None, kcoef, None, None, 1, zprev, cprev,
                                                   Lprev, sink, names_f[j], bnp, linp, j == nf - 1, rows)
         grads[names_f[j] + ".weight"] = dW
@@ -968,14 +1044,7 @@ def backward_impl(net, saved, grad_y, sink=None, after_fc=None, step_tail=None):
     if after_fc is not None:
         after_fc()
     if B > 32:  # dy is the gradient w.r.t. the pooled features: max-pool + conv5's BatchNorm backward in their own launch
-        C5, L5, g_pool = convs[4].Co, convs[4], dy
-        gsel = _empty((B, C5), grad_y)
-        dgamma, dbeta = _out(sink, bn_c[4] + ".weight", L5.bn.weight), _out(sink, bn_c[4] + ".bias", L5.bn.bias)
-        dbias = _out(sink, names_c[4] + ".bias", L5.b)
-        kcoef = _empty((3, C5), grad_y)
-        check(lib.sn_pool_backward_bn(B, C5, -1 if fixed else R, ptr(g_pool), ptr(saved["pooled"]), ptr(saved["zsel"]), ptr(gsel), ptr(cc[4]),
-                                      ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(kcoef), _st(grad_y)), "sn_pool_backward_bn")
-        grads[bn_c[4] + ".weight"], grads[bn_c[4] + ".bias"], grads[names_c[4] + ".bias"] = dgamma, dbeta, dbias
+        gsel, kcoef = _pool_bwd_bn(L5, saved, dy, fixed, sink, grads)
 
     # ---- conv stack (rows = B*N): conv5 -> ... -> conv2 (each also finishes the BatchNorm of the layer below), conv1 ----
     if step_tail is not None:  # the loss value the deferred tail writes turns NaN when a chain launch of this step timed out
@@ -985,37 +1054,7 @@ def backward_impl(net, saved, grad_y, sink=None, after_fc=None, step_tail=None):
         return grads
     if step_tail is not None:
         raise RuntimeError("backward_impl: a deferred step tail needs the one-call conv stack backward (conv_stack_backward_supported)")
-    dy = None
-    in3_floats = lib.sn_layer_backward_in3_stats_floats(R, convs[1].Ci, convs[1].Co) if (IN3_CLOSED_FORM and convs[0].Ci == 3 and not fixed) else 0
-    for i in (4, 3, 2, 1):
-        L = convs[i]
-        if i == 1 and in3_floats > 0:
-            # conv2 sits on the xyz input layer: its fused backward also yields conv1's weight gradient (closed form from
-            # three extra per-channel sums + the moments of x: no pass of its own over dY1)
-            Lp = convs[0]
-            dW = _out(sink, names_c[1] + ".weight", L.W)
-            dW0 = _out(sink, names_c[0] + ".weight", Lp.W)
-            dg, dbt = _out(sink, bn_c[0] + ".weight", Lp.bn.weight), _out(sink, bn_c[0] + ".bias", Lp.bn.bias)
-            dbs = _out(sink, names_c[0] + ".bias", Lp.b)
-            stats = _empty((in3_floats,), L.W)
-            part = _empty((lib.sn_linear_wgrad_splits(R, L.Ci, L.Co, 0) * L.Co * L.Ci,), L.W)
-            kc = _empty((3, L.Ci), L.W)
-            check(lib.sn_layer_backward_in3(R, L.Ci, L.Co, ptr(dy), ptr(zc[1]), ptr(kcoef), ptr(L.W), ptr(_z1()), ptr(cc[0]),
-                                            ptr(stats), ptr(part), ptr(dW), ptr(dg), ptr(dbt), ptr(dbs), ptr(kc),
-                                            ptr(saved["x"]), ptr(Lp.W), ptr(Lp.b), ptr(dW0), _st(L.W)), "sn_layer_backward_in3")
-            grads[names_c[1] + ".weight"], grads[names_c[0] + ".weight"] = dW, dW0
-            grads[bn_c[0] + ".weight"], grads[bn_c[0] + ".bias"], grads[names_c[0] + ".bias"] = dg, dbt, dbs
-            break
-        mode = DZ_POOL if i == 4 else DZ_BN
-        gs, ag = (gsel, saved["argsel"]) if i == 4 else (None, None)
-        dW, _, dy, dg, dbt, dbs, kc = _layer_bwd(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zc[i - 1] if i > 1 else _z1(), cc[i - 1], convs[i - 1],
-                                                 sink, names_c[i], bn_c[i - 1], names_c[i - 1], False, bn_rows)
-        grads[names_c[i] + ".weight"] = dW
-        grads[bn_c[i - 1] + ".weight"], grads[bn_c[i - 1] + ".bias"], grads[names_c[i - 1] + ".bias"] = dg, dbt, dbs
-        kcoef = kc
-    else:
-        dW, _ = _wgrad(R, convs[0], DZ_BN, dy, _z1(), kcoef, None, None, N, saved["x"].view(R, 3), None, False, sink, names_c[0])
-        grads[names_c[0] + ".weight"] = dW
+    _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink, in3=IN3_CLOSED_FORM)
     return grads
 
 

@@ -14,8 +14,9 @@ head to statistics over ALL ranks' rows, so that W ranks x B clouds train like o
             gradient), the dZ coefficients from the all-reduced sums and the global row count -- the split
             torch.nn.SyncBatchNorm makes.
 
-It runs on the layer-by-layer entry points only (one collective per BatchNorm and direction: 18 per step -- the fused
-single-node step, the FC chains and graph capture are per-rank-statistics paths and are bypassed), i.e. it is a parity mode, not
+It drives pointnet.py's layer-by-layer walk of the conv stack (_conv_stack_fwd / _conv_stack_bwd, with the coefficient and
+BatchNorm-backward steps below passed in) and runs on the layer-by-layer entry points only (one collective per BatchNorm and
+direction: 18 per step -- the fused single-node step, the FC chains and graph capture are per-rank-statistics paths and are bypassed), i.e. it is a parity mode, not
 a fast path.  The collectives go through a small communicator object so that tests can stand two "ranks" up as threads of one
 process on one GPU.
 """
@@ -24,8 +25,7 @@ import torch.distributed as dist
 
 from ._lib import check, lib, ptr
 from . import pointnet as P
-
-DZ_PLAIN, DZ_BN, DZ_POOL = 0, 1, 2
+from .pointnet import DZ_BN, DZ_PLAIN
 
 
 class DistComm:
@@ -96,19 +96,15 @@ def _global_coef(bn, coef_local, n_local, comm):
 
 def _local_coef_from_partials(L, R, stats, nblk):
     """(scale, shift, mean, invstd) of the LOCAL rows from the GEMM's (sum, sum of squares) partials; no running update."""
-    bn = L.bn
     coef = torch.empty(4, L.Co, device=L.W.device, dtype=torch.float32)
-    check(lib.sn_bn_finalize(nblk, L.Co, R, ptr(stats), ptr(bn.weight), ptr(bn.bias), float(bn.eps), 0.0, None, None, None, ptr(coef),
-                             P._st(L.W)), "sn_bn_finalize")
+    check(lib.sn_bn_finalize(nblk, L.Co, R, ptr(stats), *P._bn_args(L.bn, False, 0.0), ptr(coef), P._st(L.W)), "sn_bn_finalize")
     return coef
 
 
 def _local_coef_twopass(L, R, z):
     """The same from z itself in two passes (the FC head's rows: sum-of-squares partials lose digits there)."""
-    bn = L.bn
     coef = torch.empty(4, L.Co, device=z.device, dtype=torch.float32)
-    check(lib.sn_bn_batch_stats_twopass(R, L.Co, ptr(z), ptr(bn.weight), ptr(bn.bias), float(bn.eps), 0.0, None, None, None, ptr(coef),
-                                        P._st(z)), "sn_bn_batch_stats_twopass")
+    check(lib.sn_bn_batch_stats_twopass(R, L.Co, ptr(z), *P._bn_args(L.bn, False, 0.0), ptr(coef), P._st(z)), "sn_bn_batch_stats_twopass")
     return coef
 
 
@@ -116,19 +112,15 @@ def forward_sync(net, x_bnc, comm):
     """Training forward with synchronised statistics: y (B, 3M) and what backward_sync needs."""
     convs, fcs = P._layers(net)
     B, N, _ = x_bnc.shape
-    R = B * N
-    saved = {"x": x_bnc, "B": B, "N": N, "zc": [], "cc": [], "zf": [], "cf": [], "rows_c": [], "rows_f": []}
-    a_in, coef_prev = x_bnc.view(R, 3), None
-    for L in convs:
-        z, stats, nblk = P._linear_fwd(R, L, a_in, coef_prev, True)
+    saved = {"x": x_bnc, "B": B, "N": N, "zf": [], "cf": [], "rows_c": [], "rows_f": []}
+
+    def coef_fn(L, R, stats, nblk):
         coef, total = _global_coef(L.bn, _local_coef_from_partials(L, R, stats, nblk), R, comm)
-        saved["zc"].append(z), saved["cc"].append(coef), saved["rows_c"].append(total)
-        a_in, coef_prev = z, coef
-    C5 = convs[-1].Co
-    pooled = P._empty((B, C5), x_bnc)
-    argsel = P._empty((B, C5), x_bnc, torch.int32)
-    zsel = P._empty((B, C5), x_bnc)
-    check(lib.sn_pool_forward(B, N, C5, ptr(a_in), ptr(coef_prev), ptr(pooled), ptr(argsel), ptr(zsel), P._st(x_bnc)), "sn_pool_forward")
+        saved["rows_c"].append(total)
+        return coef
+
+    pooled, argsel, zsel = P._pool_bufs(B, convs[-1].Co, x_bnc)
+    saved["zc"], saved["cc"] = P._conv_stack_fwd(convs, x_bnc, True, (pooled, argsel, zsel), coef_fn=coef_fn)
     saved.update(pooled=pooled, argsel=argsel, zsel=zsel)
     a_in, coef_prev = pooled, None
     for L in fcs[:-1]:
@@ -143,10 +135,10 @@ def forward_sync(net, x_bnc, comm):
     return y, saved
 
 
-def _bn_backward_sync(L, coef, stats_blocks, rows_global, comm, sink, bn_name, lin_name, grads):
+def _bn_backward_sync(L, coef, stats_blocks, rows_global, comm, sink, grads):
     """BatchNorm backward of layer L from the (sum dY, sum dY Z) partials the kernels above it left: dgamma / dbeta from the local
     sums, the dZ coefficients (and the -- analytically zero -- bias gradient of the layer) from the sums of all ranks."""
-    C = L.Co
+    C, bn_name, lin_name = L.Co, L.bn_name, L.name
     local = stats_blocks.reshape(-1, 2, C).sum(0).contiguous()
     dgamma, dbeta = P._out(sink, bn_name + ".weight", L.bn.weight), P._out(sink, bn_name + ".bias", L.bn.bias)
     scratch_k = torch.empty(3, C, device=local.device, dtype=torch.float32)
@@ -162,36 +154,12 @@ def _bn_backward_sync(L, coef, stats_blocks, rows_global, comm, sink, bn_name, l
     return kcoef
 
 
-def _dgrad_z(R, L, mode, dy, z, kcoef, zprev, coef_prev):
-    """pointnet._dgrad with ZEROED statistics partials: which of the blocks a kernel variant fills depends on the route the shape
-    takes inside the library (one per 64-row tile, or one per workgroup of the fused kernels); the sum over all of them must not
-    see what it left unwritten."""
-    dyprev = torch.empty(R, L.Ci, device=L.W.device, dtype=torch.float32)
-    nblk = lib.sn_linear_stats_blocks(R)
-    stats = torch.zeros(nblk, 2, L.Ci, device=L.W.device, dtype=torch.float32) if coef_prev is not None else None
-    check(lib.sn_linear_dgrad(R, L.Ci, L.Co, mode, ptr(dy), ptr(z), ptr(kcoef), None, None, 1, ptr(L.W), ptr(zprev), ptr(coef_prev),
-                              ptr(dyprev), ptr(stats), P._st(L.W)), "sn_linear_dgrad")
-    return dyprev, stats
-
-
-def _bwd_layer_z(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, sink, name):
-    """dgrad + wgrad of one conv layer (sn_linear_backward), statistics partials zeroed (see _dgrad_z)."""
-    dW = P._out(sink, name + ".weight", L.W)
-    dyprev = torch.empty(R, L.Ci, device=L.W.device, dtype=torch.float32)
-    stats = torch.zeros(lib.sn_linear_stats_blocks(R), 2, L.Ci, device=L.W.device, dtype=torch.float32)
-    part = torch.empty(lib.sn_linear_wgrad_splits(R, L.Ci, L.Co, 0) * L.Co * L.Ci, device=L.W.device, dtype=torch.float32)
-    check(lib.sn_linear_backward(R, L.Ci, L.Co, mode, ptr(dy), ptr(z), ptr(kcoef), ptr(gsel), ptr(argsel), npts, ptr(L.W), ptr(zprev),
-                                 ptr(coef_prev), ptr(dyprev), ptr(stats), ptr(part), ptr(dW), P._st(L.W)), "sn_linear_backward")
-    return dW, dyprev, stats
-
-
 def backward_sync(net, saved, grad_y, comm, sink=None):
     """-> dict parameter name -> gradient (this rank's share: the step's gradient all-reduce averages them)."""
     convs, fcs = P._layers(net)
     B, N = saved["B"], saved["N"]
-    R = B * N
     nf = len(fcs)
-    zf, cf, zc, cc = saved["zf"], saved["cf"], saved["zc"], saved["cc"]
+    zf, cf, cc = saved["zf"], saved["cf"], saved["cc"]
     grads = {}
     dy, kcoef = grad_y.contiguous(), None
     # ---- FC head: fc_last -> ... -> fc1 -> pooled features ----
@@ -207,31 +175,22 @@ def backward_sync(net, saved, grad_y, comm, sink=None):
         grads[L.name + ".weight"] = dW
         if db is not None:
             grads[L.name + ".bias"] = db
-        dy, stats = _dgrad_z(B, L, mode, dy, z, kc, aprev, cprev)
+        # (ZEROED statistics partials, as everywhere in this mode: _bn_backward_sync sums over all the blocks itself)
+        dy, stats, _ = P._dgrad(B, L, mode, dy, z, kc, None, None, 1, aprev, cprev, zero_stats=True)
         if j > 0 and fcs[j - 1].bn is not None:
-            kcoef = _bn_backward_sync(fcs[j - 1], cf[j - 1], stats, saved["rows_f"][j - 1], comm, sink, fcs[j - 1].bn_name, fcs[j - 1].name,
-                                      grads)
+            kcoef = _bn_backward_sync(fcs[j - 1], cf[j - 1], stats, saved["rows_f"][j - 1], comm, sink, grads)
         else:
             kcoef = None
-    # ---- max-pool + conv5's BatchNorm ----
-    C5, L5 = convs[4].Co, convs[4]
+    # ---- max-pool + the last conv layer's BatchNorm ----
+    L5, C5 = convs[-1], convs[-1].Co
     gsel = P._empty((B, C5), grad_y)
     pstats = P._empty((2 * C5,), grad_y)
     check(lib.sn_pool_backward(B, C5, ptr(dy), ptr(saved["pooled"]), ptr(saved["zsel"]), ptr(gsel), ptr(pstats), P._st(grad_y)),
           "sn_pool_backward")
-    kcoef = _bn_backward_sync(L5, cc[4], pstats, saved["rows_c"][4], comm, sink, L5.bn_name, L5.name, grads)
-    # ---- conv stack: conv5 -> conv2 (each leaves the sums of the BatchNorm below), conv1 ----
-    dy = None
-    for i in (4, 3, 2, 1):
-        L = convs[i]
-        mode = DZ_POOL if i == 4 else DZ_BN
-        gs, ag = (gsel, saved["argsel"]) if i == 4 else (None, None)
-        dW, dy, stats = _bwd_layer_z(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zc[i - 1], cc[i - 1], sink, L.name)
-        grads[L.name + ".weight"] = dW
-        kcoef = _bn_backward_sync(convs[i - 1], cc[i - 1], stats, saved["rows_c"][i - 1], comm, sink, convs[i - 1].bn_name, convs[i - 1].name,
-                                  grads)
-    dW, _ = P._wgrad(R, convs[0], DZ_BN, dy, zc[0], kcoef, None, None, N, saved["x"].view(R, 3), None, False, sink, convs[0].name)
-    grads[convs[0].name + ".weight"] = dW
+    kcoef = _bn_backward_sync(L5, cc[-1], pstats, saved["rows_c"][-1], comm, sink, grads)
+    # ---- conv stack: the shared walk, each layer leaving the sums of the BatchNorm below to the all-reduce ----
+    P._conv_stack_bwd(convs, saved, gsel, kcoef, False, grads, sink,
+                      bn_bwd=lambda i, stats: _bn_backward_sync(convs[i], cc[i], stats, saved["rows_c"][i], comm, sink, grads))
     return grads
 
 

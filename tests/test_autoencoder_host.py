@@ -12,15 +12,16 @@ from torch_ae import torch_ae_copy  # noqa: E402
 def test_module_is_exported_and_adds_no_c_entry():
     """The autoencoder is built from the library's existing entries (the single-launch decoder kernels the issue proposed lost to the
     sn_skinny_linear composition and were kept out, as the issue rules for that outcome): the package exports the module and the loss,
-    and every entry the module calls is in the prototype table."""
+    and every entry the module calls -- itself or through the layer walk and the skinny-GEMM wrappers it drives (pointnet.py,
+    task_features.py) -- is in the prototype table."""
     import inspect
 
     import samplenet_amd
-    from samplenet_amd import _lib, autoencoder
+    from samplenet_amd import _lib, autoencoder, pointnet, task_features
 
     assert {"PointNetAE", "reconstruction_loss"} <= set(samplenet_amd.__all__)
     assert not [n for n in _lib.PROTOTYPES if n.startswith("sn_ae_")]
-    used = set(__import__("re").findall(r"lib\.(sn_[a-z0-9_]+)", inspect.getsource(autoencoder)))
+    used = set(__import__("re").findall(r"lib\.(sn_[a-z0-9_]+)", "".join(inspect.getsource(m) for m in (autoencoder, pointnet, task_features))))
     assert used and used <= set(_lib.PROTOTYPES), used - set(_lib.PROTOTYPES)
 
 
