@@ -354,6 +354,30 @@ int sn_pointnet_narrow_backward_supported(int R, int c1, int c2, int c3, int c4)
 int sn_pointnet_narrow_backward(int R, const float *dz4, const float *z1, const float *z2, const float *z3, const float *W1, const float *W2,
                                 const float *W3, const float *W4, void *wplanes_t, int planes_ready, float *dx, sn_stream_t stream);
 
+/* The per-cloud transforms of PointNet's classifier (classification/models/pointnet_cls.py:27-29, 55-59) and their gradients:
+ *   sn_cloud_transform_forward   Y[b] (N, K) = X[b] (N, K) . T[b] (K, K), K = 3 (VALU) or 64 (fp32 MFMA); any N >= 0.
+ *   sn_cloud_transform_backward  dX[b] = dY[b] . T[b]^T and dT[b] = X[b]^T . dY[b]; dX or dT may be NULL (not wanted; T / X may then
+ *                                be NULL too).  dT is OVERWRITTEN; every sum has one fixed order (rows ascending within a quarter of the
+ *                                cloud, the quarters added in ascending order; no atomics): two calls give the same bits.
+ * True fp32 arithmetic: integer-valued operands whose sums stay below 2^24 give exact results.
+ *   sn_orthogonality_loss_forward   loss[0] = sum over b of 1/2 |T[b] T[b]^T - I|^2 (pointnet_cls.py:124-130, tf.nn.l2_loss);
+ *                                partial: B floats of scratch (the per-cloud terms, added in ascending b).
+ *   sn_orthogonality_loss_backward  dT[b] = grad_loss[0] * 2 (T[b] T[b]^T - I) T[b]; grad_loss: device scalar.
+ *   sn_bn_relu_forward / _backward  y (R, C) = relu(scale z + shift) with coef = {scale[C], shift[C], ...} -- the activation the GEMM
+ *                                entries apply when the next layer loads its operand, materialised for a consumer that is no GEMM
+ *                                entry (the feature transform) -- and dy = g . [y > 0] for the layer's backward (with_scale != 0: times scale,
+ *                                the whole backward of a BatchNorm on FIXED statistics).  C % 4 == 0.
+ * An empty batch (B == 0; no rows) is a no-op that succeeds whatever the pointers; sn_cloud_transform_backward with dX == NULL and
+ * dT == NULL checks its arguments and launches nothing. */
+int sn_cloud_transform_forward(int B, int N, int K, const float *X, const float *T, float *Y, sn_stream_t stream);
+int sn_cloud_transform_backward(int B, int N, int K, const float *X, const float *T, const float *dY, float *dX, float *dT,
+                                sn_stream_t stream);
+int sn_orthogonality_loss_forward(int B, int K, const float *T, float *partial, float *loss, sn_stream_t stream);
+int sn_orthogonality_loss_backward(int B, int K, const float *T, const float *grad_loss, float *dT, sn_stream_t stream);
+int sn_bn_relu_forward(long long R, int C, const float *z, const float *coef, float *y, sn_stream_t stream);
+int sn_bn_relu_backward(long long R, int C, const float *z, const float *coef, const float *g, int with_scale, float *dy,
+                        sn_stream_t stream);
+
 /* Linear layers on at most 32 rows (PCRNet's trunk, registration/models/pcrnet.py:56-77): out (R, N) = act((x . [gate > 0]) (R, K) .
  * W^T + bias), the weight stream cut into (32-column tile) x (K slice) workgroups, slices summed in order by the last workgroup to
  * arrive (deterministic); fp32 products as split-bf16 MFMAs.

@@ -8,6 +8,7 @@ is missing -- there is no CPU or eager-PyTorch fallback.
 from . import _lib  # noqa: F401  (loads the HIP library or raises)
 from . import ops, sputils  # noqa: F401
 from .autoencoder import PointNetAE, reconstruction_loss  # noqa: F401
+from .classifier import PointNetCls, PointNetClsBasic, classification_loss  # noqa: F401
 from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: F401
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
@@ -15,4 +16,5 @@ from .samplers import FPSSampler, RandomSampler  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
-           "progressive_sizes", "PointNetAE", "reconstruction_loss", "sputils", "ops"]
+           "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
+           "sputils", "ops"]

@@ -128,6 +128,12 @@ PROTOTYPES = {
     "sn_pointnet_narrow_forward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "sn_pointnet_narrow_backward_supported": [_i, _i, _i, _i, _i],
     "sn_pointnet_narrow_backward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "sn_cloud_transform_forward": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "sn_cloud_transform_backward": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_orthogonality_loss_forward": [_i, _i, _vp, _vp, _vp, _vp],
+    "sn_orthogonality_loss_backward": [_i, _i, _vp, _vp, _vp, _vp],
+    "sn_bn_relu_forward": [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp],
+    "sn_bn_relu_backward": [ctypes.c_longlong, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "sn_skinny_linear_supported": [_i, _i, _i],
     "sn_skinny_linear_scratch_bytes": [_i, _i, _i],
     "sn_skinny_linear": [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],

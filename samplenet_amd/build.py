@@ -32,6 +32,7 @@ SOURCES = [
     ("pointnet_mlp_backward.hip", []),
     ("fc_chain.hip", []),
     ("task_network.hip", []),
+    ("cloud_transform.hip", []),
 ]
 # No COMPILER-GENERATED packed fp32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in device code: with a SECOND process on the same GPU
 # (two ranks on one device, a monitoring job) kernels carrying the compiler's SLP-packed f32 ops returned wrong LOW halves in ~1 %

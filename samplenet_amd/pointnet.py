@@ -211,12 +211,13 @@ def _bn_coef(L, R, stats, nblk, training):
 
 def _conv_stack_fwd(convs, x_bnc, training, pool, fuse_pool=False, coef_fn=None):
     """conv1..convN layer by layer on the (B*N, 3) rows of the cloud, then the max-pool into pool = (pooled, argsel, zsel)
+    (pool None: no max-pool, the caller consumes the last layer's output itself)
     -> (pre-BatchNorm outputs z, coefficient blocks), one per layer.  The per-layer step: training = batch statistics
     (_layer_fwd_bn; fuse_pool: the last layer's launch also pools), otherwise running statistics; coef_fn(L, R, stats, nblk) ->
     coef: the GEMM with statistics partials, then the caller's own coefficients (syncbn: statistics of all ranks)."""
     B, N, _ = x_bnc.shape
     R = B * N
-    a_in, coef = x_bnc.view(R, 3), None
+    a_in, coef = x_bnc.view(R, convs[0].Ci), None
     zs, cs = [], []
     for L in convs:
         if coef_fn is not None:
@@ -232,7 +233,7 @@ def _conv_stack_fwd(convs, x_bnc, training, pool, fuse_pool=False, coef_fn=None)
         zs.append(z)
         cs.append(coef)
         a_in = z
-    if not fuse_pool:
+    if not fuse_pool and pool is not None:
         check(lib.sn_pool_forward(B, N, convs[-1].Co, ptr(a_in), ptr(coef), ptr(pool[0]), ptr(pool[1]), ptr(pool[2]), _st(x_bnc)),
               "sn_pool_forward")
     return zs, cs
@@ -794,7 +795,8 @@ def _pool_bwd_bn(L, saved, g_pool, fixed, sink, grads):
     return gsel, kcoef
 
 
-def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=True, input_grad=False, bn_bwd=None, in3=False):
+def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=True, input_grad=False, bn_bwd=None, in3=False,
+                    dy_top=None):
     """The conv stack's backward layer by layer, convN -> conv1, from gsel (B, C): the gradient at the max-pooled points, and
     kcoef: the dZ coefficients of convN's BatchNorm.  Fills grads (written into sink where it has the name); returns the gradient
     w.r.t. the cloud (R, 3) when input_grad, else None.
@@ -804,13 +806,15 @@ def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=T
       not wgrads          a frozen stack, data gradient only (the dense sn_linear_dgrad serves the pooled top layer too: with a
                           BatchNorm its dZ is dense): sn_bn_backward_coef on the local sums, scale only when fixed;
       bn_bwd(i - 1, stats) -> kcoef   the caller's own, from ZEROED block partials behind sn_linear_backward (syncbn).
-    in3 (head only): conv2's fused backward yields conv1's weight gradient in closed form where the library supports the shape."""
+    in3 (head only): conv2's fused backward yields conv1's weight gradient in closed form where the library supports the shape.
+    dy_top (R, C): a stack WITHOUT max-pool behind it (the classifier's stacks in front of a transform) -- the dense gradient at
+    convN's BatchNorm output, ReLU mask applied, in place of gsel; kcoef as above."""
     B, N = saved["B"], saved["N"]
     R = B * N
     zc, cc, x_rows = saved["zc"], saved["cc"], saved["x"].view(R, convs[0].Ci)
     top = len(convs) - 1
     in3_floats = lib.sn_layer_backward_in3_stats_floats(R, convs[1].Ci, convs[1].Co) if (in3 and convs[0].Ci == 3 and not fixed) else 0
-    dy = None
+    dy = dy_top
     for i in range(top, 0, -1):
         L, Lp = convs[i], convs[i - 1]
         if i == 1 and in3_floats > 0:
@@ -830,7 +834,7 @@ def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=T
             grads[Lp.bn_name + ".weight"], grads[Lp.bn_name + ".bias"], grads[Lp.name + ".bias"] = dg, dbt, dbs
             return None
         # the top layer reads its dZ through the pool's selection, the others apply their BatchNorm's dZ coefficients
-        mode, gs, ag = (DZ_POOL, gsel, saved["argsel"]) if i == top else (DZ_BN, None, None)
+        mode, gs, ag = (DZ_POOL, gsel, saved["argsel"]) if i == top and dy_top is None else (DZ_BN, None, None)
         zprev = zc[i - 1] if i > 1 else _z1(convs, saved)
         if wgrads and bn_bwd is None:
             dW, _, dy, dg, dbt, dbs, kcoef = _layer_bwd(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zprev, cc[i - 1], Lp, sink, L.name,
