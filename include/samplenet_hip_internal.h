@@ -382,7 +382,10 @@ int sn_bn_relu_backward(long long R, int C, const float *z, const float *coef, c
  * W^T + bias), the weight stream cut into (32-column tile) x (K slice) workgroups, slices summed in order by the last workgroup to
  * arrive (deterministic); fp32 products as split-bf16 MFMAs.
  *   transposed == 0: W (N, K) -- forward;  != 0: W (K, N) -- data gradient dX = (dY . [y > 0]) W with gate = the layer's output y
- *   gate, bias: optional.  scratch: _scratch_bytes; counters: (N + 31) / 32 zeroed 32-bit words (left zeroed). */
+ *   gate, bias: optional.  scratch: _scratch_bytes; counters: (N + 31) / 32 zeroed 32-bit words (left zeroed).
+ * Errors, in this order: a NULL operand is SN_ERR_BAD_ARGUMENT; a size the kernel does not serve (R outside 1..128, K or N below 1:
+ * sn_skinny_linear_supported) is SN_ERR_UNSUPPORTED whatever the splits; a ksplit / nsplit that does not fit the size is
+ * SN_ERR_BAD_ARGUMENT. */
 /* sn_pcrnet_head_forward + sn_qrot_forward as ONE launch (main.py:563-571: twist = model(p0, p1); est_transform.rotate(p0)):
  * y (B,7), v (B,N,3) -> twist (B,7), quat (B,4), qnorm (device scalar, may be NULL), out (B,N,3) = v rotated by quat; and the
  * backward of that pair as one launch: grad_out (B,N,3), grad_twist (B,7), grad_quat (B,4), grad_qnorm (device scalar), each

@@ -31,6 +31,12 @@ int sn_set_error(int code, const char *fmt, ...);
         if (e_ != hipSuccess) return sn_set_error((int)e_, "%s: %s", __func__, hipGetErrorString(e_)); \
     } while (0)
 
+#define SN_LAUNCH_CHECK_AS(who)                                                                  \
+    do {                                                                                         \
+        hipError_t e_ = hipGetLastError();                                                       \
+        if (e_ != hipSuccess) return sn_set_error((int)e_, "%s: %s", who, hipGetErrorString(e_)); \
+    } while (0)
+
 typedef unsigned long long sn_u64;
 
 // More than 64 KB of dynamic LDS must be requested per kernel with hipFuncSetAttribute -- and the attribute is PER DEVICE: a

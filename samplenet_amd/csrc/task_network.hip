@@ -955,28 +955,17 @@ extern "C" long long sn_skinny_linear_scratch_bytes(int R, int K, int N)
     const int rt = R <= 32 ? 1 : R <= 64 ? 2 : 4;
     return (long long)S * ((N + 31) / 32) * rt * 1024 * (long long)sizeof(float);
 }
-// counters: (N + 31) / 32 zeroed 32-bit words (left zeroed).  transposed != 0: W is (K, N) (the data gradient through a layer
-// whose weight is (Co = K, Ci = N)).
-extern "C" int sn_skinny_linear2(int R, int K, int N, const float *x, const float *x2, int ksplit, const float *gate, const float *W,
-                                 int transposed, const float *bias, int relu, float *out, float *out2, int nsplit, float *scratch,
-                                 unsigned *counters, sn_stream_t stream);
-extern "C" int sn_skinny_linear(int R, int K, int N, const float *x, const float *gate, const float *W, int transposed, const float *bias,
-                                int relu, float *out, float *scratch, unsigned *counters, sn_stream_t stream)
+// The shared body of the two entries.  Errors carry the name of the entry that was called.  Precedence: NULL operands (BAD), then a
+// size the kernel does not serve (UNSUPPORTED), then the operand splits measured against that size (BAD) -- N = 0 is UNSUPPORTED,
+// not a bad nsplit, and 129 rows with a bad ksplit are UNSUPPORTED too.
+static int skinny_linear_impl(const char *who, int R, int K, int N, const float *x, const float *x2, int ksplit, const float *gate,
+                              const float *W, int transposed, const float *bias, int relu, float *out, float *out2, int nsplit,
+                              float *scratch, unsigned *counters, sn_stream_t stream)
 {
-    SN_REQUIRE(out, "null pointer");
-    return sn_skinny_linear2(R, K, N, x, nullptr, 0, gate, W, transposed, bias, relu, out, nullptr, 0, scratch, counters, stream);
-}
-// The two-part form: x2 / ksplit -- input columns k >= ksplit come from x2 (R, K - ksplit), x is (R, ksplit) (x2 == NULL: x is (R, K));
-// out2 / nsplit -- output columns n >= nsplit go to out2 (R, N - nsplit), out is (R, nsplit) (nsplit == 0: out is (R, N)); with
-// nsplit > 0 either output may be NULL (that part is not wanted).
-extern "C" int sn_skinny_linear2(int R, int K, int N, const float *x, const float *x2, int ksplit, const float *gate, const float *W,
-                                 int transposed, const float *bias, int relu, float *out, float *out2, int nsplit, float *scratch,
-                                 unsigned *counters, sn_stream_t stream)
-{
-    SN_REQUIRE(x && W && scratch && counters, "null pointer");
-    SN_REQUIRE(!x2 || (ksplit > 0 && ksplit < K && ksplit % 8 == 0 && !gate), "x2: ksplit must be a multiple of 8 inside (0, K), no gate");
-    SN_REQUIRE(nsplit >= 0 && nsplit < N && (nsplit > 0 ? (out || out2) : out != nullptr), "bad output split");
-    if (!sn_skinny_linear_supported(R, K, N)) return sn_set_error(SN_ERR_UNSUPPORTED, "sn_skinny_linear: needs at most 128 rows");
+    SN_REQUIRE_AS(who, x && W && scratch && counters, "null pointer");
+    if (!sn_skinny_linear_supported(R, K, N)) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: needs 1 to 128 rows, K >= 1, N >= 1", who);
+    SN_REQUIRE_AS(who, !x2 || (ksplit > 0 && ksplit < K && ksplit % 8 == 0 && !gate), "x2: ksplit must be a multiple of 8 inside (0, K), no gate");
+    SN_REQUIRE_AS(who, nsplit >= 0 && nsplit < N && (nsplit > 0 ? (out || out2) : out != nullptr), "bad output split");
     SkinnyArgs g{};
     g.x = x, g.gate = gate, g.W = W, g.bias = bias, g.out = out, g.part = scratch, g.counter = counters;
     g.R = R, g.K = K, g.N = N, g.wmode = transposed ? 1 : 0, g.relu = relu;
@@ -996,8 +985,25 @@ extern "C" int sn_skinny_linear2(int R, int K, int N, const float *x, const floa
     else if (R <= 64) SN_SK_LAUNCH(2);
     else SN_SK_LAUNCH(4);
 #undef SN_SK_LAUNCH
-    SN_LAUNCH_CHECK();
+    SN_LAUNCH_CHECK_AS(who);
     return 0;
+}
+// counters: (N + 31) / 32 zeroed 32-bit words (left zeroed).  transposed != 0: W is (K, N) (the data gradient through a layer
+// whose weight is (Co = K, Ci = N)).
+extern "C" int sn_skinny_linear(int R, int K, int N, const float *x, const float *gate, const float *W, int transposed, const float *bias,
+                                int relu, float *out, float *scratch, unsigned *counters, sn_stream_t stream)
+{
+    SN_REQUIRE(out, "null pointer");
+    return skinny_linear_impl(__func__, R, K, N, x, nullptr, 0, gate, W, transposed, bias, relu, out, nullptr, 0, scratch, counters, stream);
+}
+// The two-part form: x2 / ksplit -- input columns k >= ksplit come from x2 (R, K - ksplit), x is (R, ksplit) (x2 == NULL: x is (R, K));
+// out2 / nsplit -- output columns n >= nsplit go to out2 (R, N - nsplit), out is (R, nsplit) (nsplit == 0: out is (R, N)); with
+// nsplit > 0 either output may be NULL (that part is not wanted).
+extern "C" int sn_skinny_linear2(int R, int K, int N, const float *x, const float *x2, int ksplit, const float *gate, const float *W,
+                                 int transposed, const float *bias, int relu, float *out, float *out2, int nsplit, float *scratch,
+                                 unsigned *counters, sn_stream_t stream)
+{
+    return skinny_linear_impl(__func__, R, K, N, x, x2, ksplit, gate, W, transposed, bias, relu, out, out2, nsplit, scratch, counters, stream);
 }
 
 // ---- weight gradient of those layers (round 4: a TRAINABLE trunk stays on the library -- registration/main.py --train-pcrnet,

@@ -1,7 +1,9 @@
 """Host-side half of the C-ABI contract (no GPU): every geometric entry point of include/samplenet_hip.h refuses a negative
 size, a NULL required pointer, an unknown layout selector and an unsupported K / prefix count / matching size with the
 documented code and its OWN name in sn_last_error_string(), and treats the documented empty cases as no-ops -- all of it before
-any device work.  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+any device work.  So do the entries of include/samplenet_hip_internal.h that the task networks share: the skinny FC route
+(sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
+transforms, the orthogonality regulariser and sn_bn_relu_*.  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 import json
@@ -52,10 +54,32 @@ ENTRIES = {
     "sn_prefix_point_minima": ([1, 8, 4, 1, HOSTI, Pp, Pp, Pp, Pp, None], [0, 1, 2, 3], [4, 5, 6, 7, 8]),
     "sn_nn_matching": ([1, 8, 4, Pp, 0, Pp, 1, Pp, None], [0, 1, 2], [3, 5, 7]),
 }
+# The entries of include/samplenet_hip_internal.h that the task networks share, under the same rules as ENTRIES (kept apart: ENTRIES
+# is the public header's list, which tests/test_gpu_cabi_contract.py walks family by family): the shared FC route's weight gradient,
+# the per-cloud transforms (K counts as a size: -1 is as bad as any K outside {3, 64}), the orthogonality regulariser, the
+# materialised BatchNorm + ReLU (its R is a long long: cases below)
+INTERNAL = {
+    "sn_skinny_wgrad": ([4, 8, 8, Pp, None, 0, Pp, None, Pp, None, None], [0, 1, 2], [3, 6, 8]),
+    "sn_cloud_transform_forward": ([1, 8, 3, Pp, Pp, Pp, None], [0, 1, 2], [3, 4, 5]),
+    "sn_cloud_transform_backward": ([1, 8, 3, Pp, Pp, Pp, Pp, Pp, None], [0, 1, 2], [3, 4, 5]),
+    "sn_orthogonality_loss_forward": ([1, 3, Pp, Pp, Pp, None], [0, 1], [2, 3, 4]),
+    "sn_orthogonality_loss_backward": ([1, 3, Pp, Pp, Pp, None], [0, 1], [2, 3, 4]),
+    "sn_bn_relu_forward": ([2, 8, Pp, Pp, Pp, None], [1], [2, 3, 4]),
+    "sn_bn_relu_backward": ([2, 8, Pp, Pp, Pp, 0, Pp, None], [1], [2, 3, 4, 6]),
+}
+# sn_skinny_linear / sn_skinny_linear2 answer a size they do not serve -- negative ones included -- with UNSUPPORTED (callers ask
+# sn_skinny_linear_supported and take another route), so the generic "negative size is a BAD argument" rule above does not fit them:
+# entry -> (valid argument list, required pointers); every case is spelled out in _skinny_cases().
+SKINNY = {
+    # R, K, N, x, gate, W, transposed, bias, relu, out, scratch, counters, stream
+    "sn_skinny_linear": ([4, 64, 40, Pp, None, Pp, 0, None, 0, Pp, Pp, Pp, None], [3, 5, 9, 10, 11]),
+    # R, K, N, x, x2, ksplit, gate, W, transposed, bias, relu, out, out2, nsplit, scratch, counters, stream
+    "sn_skinny_linear2": ([4, 64, 40, Pp, None, 0, None, Pp, 0, None, 0, Pp, None, 0, Pp, Pp, None], [3, 7, 11, 14, 15]),
+}
 
 
 def _with(name, changes):
-    args = list(ENTRIES[name][0])
+    args = list((ENTRIES.get(name) or INTERNAL.get(name) or SKINNY[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -63,7 +87,7 @@ def _with(name, changes):
 
 def _cases():
     out = []  # (id, entry, args, expected code, text the message must contain | None)
-    for name, (base, sizes, required) in ENTRIES.items():
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()):
         for pos in sizes:
             out.append(("%s-size%d-negative" % (name, pos), name, _with(name, {pos: -1}), BAD, name))
         for pos in required:
@@ -119,11 +143,62 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
+    return out + _skinny_cases() + _transform_cases(nulled)
+
+
+def _skinny_cases():
+    out = []
+    for name, (base, required) in SKINNY.items():
+        for pos in required:
+            out.append(("%s-arg%d-null" % (name, pos), name, _with(name, {pos: None}), BAD, name))
+        for pos, vals in ((0, (0, 129, -1)), (1, (0, -1)), (2, (0, -1))):
+            for v in vals:
+                out.append(("%s-size%d-is-%d" % (name, pos, v), name, _with(name, {pos: v}), UNSUP, name))
+    two = "sn_skinny_linear2"
+    for cid, ch in (("x2-with-gate", {4: Pp, 5: 8, 6: Pp}), ("ksplit-12", {4: Pp, 5: 12}), ("ksplit-0", {4: Pp, 5: 0}),
+                    ("ksplit-K", {4: Pp, 5: 64}), ("ksplit-negative", {4: Pp, 5: -8}), ("ksplit-past-K", {4: Pp, 5: 72}),
+                    ("nsplit-negative", {13: -1}), ("nsplit-N", {12: Pp, 13: 40}), ("nsplit-past-N", {12: Pp, 13: 41}),
+                    ("nsplit0-out-null", {11: None, 12: Pp}), ("nsplit-both-outputs-null", {11: None, 12: None, 13: 8})):
+        out.append((two + "-" + cid, two, _with(two, {**ch}), BAD, two))
+    # the documented precedence: a size that is not served is UNSUPPORTED whatever the splits; a NULL operand is BAD whatever the size
+    out.append((two + "-R129-with-bad-ksplit", two, _with(two, {0: 129, 4: Pp, 5: 12}), UNSUP, two))
+    out.append((two + "-R129-with-bad-nsplit", two, _with(two, {0: 129, 13: -1}), UNSUP, two))
+    out.append((two + "-R129-with-null-W", two, _with(two, {0: 129, 7: None}), BAD, two))
+    wg = "sn_skinny_wgrad"
+    for cid, ch in (("R0", {0: 0}), ("R257", {0: 257}), ("K0", {1: 0}), ("N0", {2: 0}), ("ksplit-0", {4: Pp, 5: 0}),
+                    ("ksplit-K", {4: Pp, 5: 8}), ("ksplit-negative", {4: Pp, 5: -1})):
+        out.append((wg + "-" + cid, wg, _with(wg, ch), BAD, wg))
+    return out
+
+
+def _transform_cases(nulled):
+    out = []
+    tf, tb, of, ob = "sn_cloud_transform_forward", "sn_cloud_transform_backward", "sn_orthogonality_loss_forward", "sn_orthogonality_loss_backward"
+    for name, kpos in ((tf, 2), (tb, 2), (of, 1), (ob, 1)):
+        for k in (0, 1, 2, 4, 63, 65):
+            out.append(("%s-K%d" % (name, k), name, _with(name, {kpos: k}), BAD, "K must be 3 or 64"))
+    # B > 65535: the transform kernels put the cloud on the grid's second dimension, which ends there; the orthogonality kernels put it on
+    # the first and document no such limit, so there is no such case for them
+    for name in (tf, tb):
+        out.append((name + "-B65536", name, _with(name, {0: 65536}), BAD, "65535"))
+    # sn_cloud_transform_backward: an output's other operand is required only with that output
+    out.append((tb + "-dX-without-T", tb, _with(tb, {4: None, 7: None}), BAD, tb))
+    out.append((tb + "-dT-without-X", tb, _with(tb, {3: None, 6: None}), BAD, tb))
+    out.append((tb + "-no-output-checks-dY", tb, _with(tb, {5: None, 6: None, 7: None}), BAD, tb))
+    out.append((tb + "-no-output-launches-nothing", tb, _with(tb, {3: None, 4: None, 6: None, 7: None}), 0, None))
+    for name in ("sn_bn_relu_forward", "sn_bn_relu_backward"):
+        out.append((name + "-R-negative", name, _with(name, {0: -1}), BAD, name))
+        for c in (1, 2, 6, 63):
+            out.append(("%s-C%d" % (name, c), name, _with(name, {1: c}), BAD, "multiple of 4"))
+    for name, ch in ((tf, {0: 0}), (tf, {1: 0}), (tb, {0: 0}), (of, {0: 0}), (ob, {0: 0}), ("sn_bn_relu_forward", {0: 0}),
+                     ("sn_bn_relu_forward", {1: 0}), ("sn_bn_relu_backward", {0: 0}), ("sn_bn_relu_backward", {1: 0})):
+        out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
     return out
 
 
 CASES = _cases()
-IN_SCOPE = sorted(ENTRIES) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits"]
+IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
+                                               "sn_skinny_linear_scratch_bytes"]
 
 _CHILD = r"""
 import ctypes, json, sys
@@ -154,7 +229,7 @@ def results():
 def test_the_table_walks_every_entry_in_scope():
     from samplenet_amd import _lib
 
-    for name, (base, sizes, required) in ENTRIES.items():
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()):
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto), name
         for pos, ty in enumerate(proto):
@@ -164,6 +239,12 @@ def test_the_table_walks_every_entry_in_scope():
                 assert ty is ctypes.c_void_p, (name, pos)
             if ty is ctypes.c_void_p:
                 assert base[pos] in (Pp, HOSTI, None), (name, pos)
+    for name, (base, required) in SKINNY.items():
+        proto = _lib.PROTOTYPES[name]
+        assert len(base) == len(proto) and proto[:3] == [ctypes.c_int] * 3, name
+        for pos, ty in enumerate(proto):
+            assert (ty is ctypes.c_void_p) == (base[pos] in (Pp, None)), (name, pos)
+            assert pos not in required or base[pos] == Pp, (name, pos)
     assert not [n for n in IN_SCOPE if n not in _lib.PROTOTYPES]
     assert len({c[0] for c in CASES}) == len(CASES)
 
@@ -192,3 +273,23 @@ def test_size_queries():
         s = lib.sn_soft_bwd_splits(b, m)
         assert 1 <= s <= max(1, (m + 3) // 4)
     assert lib.sn_soft_bwd_splits(32, 64) == 16 and lib.sn_soft_bwd_splits(1, 64) == 16 and lib.sn_soft_bwd_splits(2048, 64) == 1
+
+
+# (K, N) -> K slices of csrc/task_network.hip's skinny_plan, evaluated by hand: one slice, scalar and vector operand loads, partial
+# batches of the eight-at-a-time slice sum (9, 17, 25), slices of 2 and 4 k-steps (584, 1024, 2048, 4096)
+SKINNY_SLICES = {(1, 1): 1, (7, 5): 1, (61, 33): 1, (64, 7): 1, (72, 40): 2, (130, 100): 3, (200, 64): 4, (576, 33): 9, (584, 70): 5,
+                 (1088, 20): 17, (1600, 3): 25, (1024, 512): 8, (2048, 1024): 8, (4096, 64): 16}
+
+
+def test_skinny_size_queries():
+    """sn_skinny_linear_supported / _scratch_bytes are pure host functions: 1..128 rows, K and N at least 1; the scratch is
+    slices x 32-column tiles x row tiles (1, 2 or 4 tiles of 32 rows) x 4096 bytes."""
+    from samplenet_amd._lib import lib
+
+    for R, K, N, ok in ((1, 1, 1, 1), (128, 4096, 6144, 1), (0, 8, 8, 0), (129, 8, 8, 0), (-1, 8, 8, 0), (4, 0, 8, 0), (4, 8, 0, 0),
+                        (4, -1, 8, 0), (4, 8, -1, 0)):
+        assert lib.sn_skinny_linear_supported(R, K, N) == ok, (R, K, N)
+    for (K, N), slices in SKINNY_SLICES.items():
+        for R in (1, 5, 31, 32, 33, 64, 65, 97, 128):
+            rt = 1 if R <= 32 else 2 if R <= 64 else 4
+            assert lib.sn_skinny_linear_scratch_bytes(R, K, N) == slices * ((N + 31) // 32) * rt * 4096, (R, K, N)
