@@ -485,6 +485,30 @@ int sn_linear_forward_rows(int R, int Ci, int Co, const float *ain, const float 
 int sn_emd_loss_fast(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *grad1, float *grad2,
                      float *temp, sn_stream_t stream);
 
+/* The Adam update of every parameter of an optimizer group in ONE launch (samplenet_amd/optim.py; registration/main.py:167
+ * torch.optim.Adam, classification/train_samplenet.py:194 tf.train.AdamOptimizer).  Replaces no reference C interface.
+ *   chunks   device table of nchunks 32-byte entries { float *param; const float *grad; long long moment_offset; int count; int pad }:
+ *            workgroup c updates `count` (1 .. sn_adam_chunk_elems()) consecutive elements; a chunk never straddles two tensors;
+ *            moment_offset (elements, a multiple of 4) addresses both moment buffers; grad == NULL: the chunk is skipped (parameter
+ *            and moments untouched, as torch does for p.grad is None).  param / grad need only 4-byte alignment (16-byte accesses
+ *            are used where the address allows them).
+ *   exp_avg, exp_avg_sq   the flat fp32 moment buffers (16-byte aligned, distinct)
+ *   state    sn_adam_state_bytes() = 64 bytes on the device, 8-byte aligned: { double lr; double beta1^t; double beta2^t; long long t;
+ *            unsigned arrival counter (zero between launches); padding }.  The launch reads t, corrects the bias with t + 1 (fp64,
+ *            once per workgroup) and its last workgroup to arrive writes t + 1 and the advanced powers: nothing the host passes
+ *            changes from step to step, so a captured launch replays as it is.  lr is changed by a stream-ordered write of word 0.
+ *   per element (fp32, g1 alone formed in fp64 and rounded once; operation order pinned in csrc/optimizer.hip):
+ *            g1 = grad * grad_scale + weight_decay * p,
+ *            m' = beta1 m + (1 - beta1) g1, v' = beta2 v + (1 - beta2) g1^2, bc_i = 1 - beta_i^(t+1),
+ *            tf_epsilon == 0 (torch): p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps)
+ *            tf_epsilon != 0 (TensorFlow): p' = p - (lr sqrt(bc2) / bc1) m' / (sqrt(v') + eps)
+ *   grad_scale folds the 1 / world of a SUM all-reduce into the update (1 when the reducer averages).
+ * nchunks == 0 is a no-op that succeeds (the step count does not advance). */
+int sn_adam_chunk_elems(void);
+long long sn_adam_state_bytes(void);
+int sn_adam_update(int nchunks, const void *chunks, float *exp_avg, float *exp_avg_sq, void *state, double beta1, double beta2,
+                   double eps, double weight_decay, double grad_scale, int tf_epsilon, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ Importing the package loads libsamplenet_hip.so (hand-written HIP for gfx950) an
 is missing -- there is no CPU or eager-PyTorch fallback.
 """
 from . import _lib  # noqa: F401  (loads the HIP library or raises)
-from . import ops, sputils  # noqa: F401
+from . import ops, optim, sputils  # noqa: F401
 from .autoencoder import PointNetAE, reconstruction_loss  # noqa: F401
 from .classifier import PointNetCls, PointNetClsBasic, classification_loss  # noqa: F401
 from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: F401
@@ -17,4 +17,4 @@ from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
            "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
-           "sputils", "ops"]
+           "sputils", "ops", "optim"]

@@ -17,8 +17,21 @@ import torch
 class SamplerTrainStep:
     def __init__(self, net, example_x, alpha=0.01, lmbda=0.01, gamma=1.0, delta=0.0, task_loss=None, reducer=None,
                  use_graph=True, warmup=3, fused_loss=True, input_ring=None, fused_head=True, overlap_allreduce=None,
-                 allreduce="graph"):
+                 allreduce="graph", optimizer=None):
         self.net, self.reducer = net, reducer
+        # optimizer: a samplenet_amd.optim.Adam over the net's parameters -- its update (one launch per parameter group) is issued
+        # right behind reducer.reduce(): as the last node(s) of the step's graph where the gradients are final inside it (no
+        # collective, or allreduce 'graph' / 'graph-fork'), behind the Python-side collective otherwise ('after', the split step),
+        # eagerly when use_graph=False.  The graph must see one fixed set of gradient addresses: a reducer is required.
+        if optimizer is not None:
+            from .optim import Adam
+
+            if not isinstance(optimizer, Adam):
+                raise TypeError("optimizer: a samplenet_amd.optim.Adam (got %s); step any other optimizer yourself behind the call"
+                                % type(optimizer).__name__)
+            if reducer is None:
+                raise ValueError("optimizer= needs a gradient sink (FlatGradAllReducer): the update reads one fixed set of .grad tensors")
+        self.optimizer = optimizer
         self.alpha, self.lmbda, self.gamma, self.delta = alpha, lmbda, gamma, delta
         self.fused_loss = fused_loss  # False: compose the loss op by op through the module's own methods (A/B, tests)
         self.fused_head = fused_head  # fast path only: fc4's forward computed inside the pair scan (fused_step.py)
@@ -34,6 +47,7 @@ class SamplerTrainStep:
             if self.ring is not None:
                 raise ValueError("input_ring needs the captured step; synchronised BatchNorm runs eagerly")
             use_graph = False
+        self.use_graph = bool(use_graph)
         self.x = example_x.clone() if self.ring is None else self.ring[0]
         self._one = torch.ones((), device=example_x.device, dtype=torch.float32)
         self.graph = None
@@ -83,6 +97,10 @@ class SamplerTrainStep:
 
         ring = self.ring
         times = {}
+        # The probes are captured WITHOUT the optimizer: their 3 x (3 + replays) timed replays would otherwise train the model while
+        # the step is being constructed (chosen over snapshotting parameters, moments and the state block: nothing to restore, and
+        # the update is the same node behind every placement, so it does not change which one wins).
+        optimizer, self.optimizer = self.optimizer, None
         for mode in ("graph", "after", "graph-fork"):
             self.allreduce, self.in_graph = mode, mode != "after"
             self._ring_graphs, self._ring_loss, self._ring_outputs = [], [], []
@@ -129,6 +147,7 @@ class SamplerTrainStep:
         self.allreduce_probe = {"ms_per_step": dict(zip(("graph", "after", "graph-fork"), vals)), "chosen": best, "replays": replays}
         self.allreduce, self.in_graph = best, best != "after"
         self._ring_graphs, self._ring_loss, self._ring_outputs = [], [], []
+        self.optimizer = optimizer
         self._capture(1)
 
     def _probe_step(self):
@@ -285,6 +304,8 @@ class SamplerTrainStep:
                     loss = self._step()
                     if self.in_graph:
                         self.reducer.reduce()  # captured: the collective(s) replay with the step
+                    if self._update_in_graph():
+                        self.optimizer._launch()  # captured: the update replays with the step
             finally:
                 if fork:
                     self.reducer.capture_fork = False
@@ -330,6 +351,16 @@ class SamplerTrainStep:
                 if self.reducer is None:
                     for p in self.net.parameters():
                         p.grad = None
+            # (the warm-up passes carry no update: constructing the step does not train.  The chunk table is uploaded here, from the
+            #  bucket's views, and cannot move afterwards)
+            if self.optimizer is not None:
+                self.reducer._rebind()
+                self.optimizer.prepare()
+                lo = self.reducer.flat.data_ptr()
+                hi = lo + 4 * self.reducer.flat.numel()
+                if not all(lo <= p.grad.data_ptr() < hi for dev in self.optimizer._dev for p in dev.updated):
+                    raise ValueError("optimizer=: a parameter's gradient lies outside the reducer's bucket; the captured update "
+                                     "needs fixed gradient addresses")
         torch.cuda.current_stream().wait_stream(side)
         from .surface import _collect_before_capture
 
@@ -363,6 +394,24 @@ class SamplerTrainStep:
         # for as long as the graphs, whatever happens to the module's own list
         self._plan_refs = list(self.net.__dict__.get("_sn_plans", ()))
 
+    def _update_in_graph(self):
+        """The update is a node of the step's graph when nothing has to run between the graph and it: no collective at all, or the
+        collective inside the graph.  (Behind the Python-side collective of 'after' and behind graph 2 of the split step it is a
+        launch of its own.)"""
+        return self.optimizer is not None and self.use_graph and not self.split and (self.in_graph or not self.reducer.collective)
+
+    def _update(self, replayed):
+        """Behind reducer.reduce() of every step: the update itself unless the replayed graph carried it, and the version bumps
+        of the parameters it wrote (the package's weight caches are keyed on them)."""
+        if self.optimizer is None:
+            return
+        if not replayed:
+            self.optimizer.step()  # eager step: the full host side (gradients are whatever the reducer bound)
+            return
+        if not self._update_in_graph():
+            self.optimizer._launch()
+        self.optimizer._mark_updated()
+
     def _replay_graphs(self, i):
         graphs = self._ring_graphs[i]
         graphs[0].replay()
@@ -376,12 +425,15 @@ class SamplerTrainStep:
         if self.ring is None:
             raise RuntimeError("replay(i) needs an input ring; call the step with a batch instead")
         if self._ring_graphs:
+            if self.optimizer is not None:
+                self.optimizer._sync_lr()  # (the host side of step(): the table cannot move under a captured step)
             self._replay_graphs(i)
         else:
             self.x = self.ring[i]
             self.loss = self._step()
         if self.reducer is not None:
             self.reducer.reduce(collective=not (self.in_graph and self._ring_graphs), replayed=bool(self._ring_graphs))
+        self._update(bool(self._ring_graphs))
         return self.loss
 
     def check(self):
@@ -400,9 +452,12 @@ class SamplerTrainStep:
             raise RuntimeError("this step was built on an input ring: fill input_ring[i] in place and call replay(i)")
         self.x.copy_(x, non_blocking=True)
         if self._ring_graphs:
+            if self.optimizer is not None:
+                self.optimizer._sync_lr()  # (the host side of step(): the table cannot move under a captured step)
             self._replay_graphs(0)
         else:
             self.loss = self._step()
         if self.reducer is not None:
             self.reducer.reduce(collective=not (self.in_graph and self._ring_graphs), replayed=bool(self._ring_graphs))
+        self._update(bool(self._ring_graphs))
         return self.loss
