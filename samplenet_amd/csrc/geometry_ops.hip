@@ -1009,12 +1009,13 @@ __global__ void __launch_bounds__(64) chamfer_mean_grouped_final_kernel(int n2, 
     loss[e] = c12 + 1.0f * c21;
 }
 
-static int group_sizes(int R, int n1, int group, int nev, const int *nvalid, GroupSizes &gs)
+// (`who` names the entry in the error text)
+static int group_sizes(const char *who, int R, int n1, int group, int nev, const int *nvalid, GroupSizes &gs)
 {
-    SN_REQUIRE(group >= 1 && nev >= 1 && nev <= kMaxPrefixes && R == nev * group && nvalid, "R = nev * group, at most 16 evaluations");
+    SN_REQUIRE_AS(who, group >= 1 && nev >= 1 && nev <= kMaxPrefixes && R == nev * group && nvalid, "R = nev * group, at most 16 evaluations");
     gs.n = nev;
     for (int e = 0; e < nev; ++e) {
-        SN_REQUIRE(nvalid[e] >= 1 && nvalid[e] <= n1, "valid points outside [1, n1]");
+        SN_REQUIRE_AS(who, nvalid[e] >= 1 && nvalid[e] <= n1, "valid points outside [1, n1]");
         gs.nv[e] = nvalid[e];
     }
     return 0;
@@ -1026,7 +1027,7 @@ extern "C" int sn_chamfer_mean_loss_forward_grouped(int R, int n1, int n2, int g
 {
     SN_REQUIRE(R >= 1 && n1 >= 1 && n2 >= 1 && dist1 && dist2 && partial && loss, "bad argument");
     GroupSizes gs{};
-    if (int rc = group_sizes(R, n1, group, nev, nvalid, gs)) return rc;
+    if (int rc = group_sizes(__func__, R, n1, group, nev, nvalid, gs)) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(chamfer_mean_grouped_partial_kernel, dim3(R), dim3(256), 0, st, n1, n2, group, gs, dist1, dist2, partial);
     hipLaunchKernelGGL(chamfer_mean_grouped_final_kernel, dim3(1), dim3(64), 0, st, n2, group, gs, partial, loss);
@@ -1110,7 +1111,7 @@ extern "C" int sn_chamfer_mean_loss_backward_grouped(int R, int n1, const float 
     SN_REQUIRE(R >= 1 && n1 >= 1 && n2 >= 1 && n1 <= 2048 && n2 <= 2048, "bad size (at most 2048 points a side)");
     SN_REQUIRE(xyz1 && xyz2 && idx1 && idx2 && grad_loss, "null pointer");
     GroupedGrad gg{};
-    if (int rc = group_sizes(R, n1, group, nev, nvalid, gg.gs)) return rc;
+    if (int rc = group_sizes(__func__, R, n1, group, nev, nvalid, gg.gs)) return rc;
     gg.gL = grad_loss, gg.group = group;
     for (int e = 0; e < nev; ++e) gg.c_pad[e] = 1.0f / ((float)group * (float)nvalid[e]);
     gg.c_full = 1.0f / ((float)group * (float)n2);

@@ -616,7 +616,8 @@ class PCRNet(nn.Module):
     def _one_batch_ok(self, x0, x1_list, feat0=None):
         """Several evaluations against one template as ONE batch through extractor, trunk, head + rotation and Chamfer term
         (_pcrnet_chamfer_loss_multi): 'bnc' clouds on the GPU, at most 16 of them and 128 trunk rows, the padded batch below ~2.5 x
-        the clouds' own points, at most 2048 points a side (the grouped Chamfer backward keeps a cloud in registers)."""
+        the clouds' own points, every cloud's own pass above 64 rows (_padding_keeps_bits), at most 2048 points a side (the grouped
+        Chamfer backward keeps a cloud in registers)."""
         E = len(x1_list)
         if not (1 < E <= 16 and self.input_shape == "bnc" and x0.is_cuda and type(self.feat) is PointNetFeatures):
             return False
@@ -626,8 +627,16 @@ class PCRNet(nn.Module):
         B = x0.shape[0]
         K2 = self.fc1.in_features // 2
         return (E * B <= 128 and K2 % 8 == 0 and max(sizes) * E <= 2.5 * sum(sizes) and max(sizes) <= 2048 and x0.shape[1] <= 2048
+                and self._padding_keeps_bits(B, sizes)
                 and all(x.dim() == 3 and x.shape[0] == B and x.shape[2] == 3 for x in x1_list)
                 and not any(p.requires_grad for p in self.parameters()))
+
+    @staticmethod
+    def _padding_keeps_bits(B, sizes):
+        """A cloud repeated cyclically keeps its pooled features bit for bit only while its OWN extractor pass runs the kernels the
+        padded batch runs: at 64 rows or fewer (B points-per-cloud) the layers take the few-row kernels (and the xyz layer not the
+        streaming one), whose sums are ordered differently -- such clouds are evaluated one by one."""
+        return B * min(sizes) > 64
 
     def forward_multi_one_batch(self, x0, x1_list, feat0=None):
         """forward_multi with everything batched: -> (twist (E B, 7), y (E B, 7), qnorm (E,), quat (E B, 4), rotated template
@@ -650,11 +659,13 @@ class PCRNet(nn.Module):
         """self.feat of several source clouds, concatenated over the batch.  Clouds of DIFFERENT sizes (the progressive sampler's
         prefixes) go through the extractor as ONE batch: every cloud repeated cyclically up to the largest size (ops.cyclic_pad_cat) --
         the extractor has no BatchNorm and reduces over the points with a maximum only, so the copies change nothing (bit for bit) --
-        instead of one latency-bound pass per cloud.  Taken while the padded batch stays below ~2.5 x the clouds' own points."""
+        instead of one latency-bound pass per cloud.  Taken while the padded batch stays below ~2.5 x the clouds' own points and every
+        cloud's own pass would run above 64 rows (_padding_keeps_bits)."""
         sizes = [x.shape[1] if self.input_shape == "bnc" else x.shape[2] for x in x1_list]
         P = max(sizes)
         if (len(x1_list) > 1 and len(set(sizes)) > 1 and len(x1_list) <= 16 and self.input_shape == "bnc" and x1_list[0].is_cuda
-                and P * len(sizes) <= 2.5 * sum(sizes) and type(self.feat) is PointNetFeatures):
+                and P * len(sizes) <= 2.5 * sum(sizes) and type(self.feat) is PointNetFeatures
+                and self._padding_keeps_bits(x1_list[0].shape[0], sizes)):
             from .ops import cyclic_pad_cat
 
             return self.feat(cyclic_pad_cat(x1_list))  # (E B, K)

@@ -3,7 +3,8 @@ size, a NULL required pointer, an unknown layout selector and an unsupported K /
 documented code and its OWN name in sn_last_error_string(), and treats the documented empty cases as no-ops -- all of it before
 any device work.  So do the entries of include/samplenet_hip_internal.h that the task networks share: the skinny FC route
 (sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
-transforms, the orthogonality regulariser and sn_bn_relu_*.  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+transforms, the orthogonality regulariser and sn_bn_relu_*, and the nine entries of the one-batch task evaluation (cyclic padding, the
+valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 import json
@@ -17,6 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD, UNSUP = 10001, 10002
 Pp = "PTR"    # a non-NULL (never dereferenced) device pointer
 HOSTI = "HOSTI"  # a real host int array {4}: sn_prefix_point_minima reads its prefix sizes on the host
+HOSTP = "HOSTP"  # a real host array of ONE non-NULL (never dereferenced) device pointer: sn_cyclic_pad_cat reads its clouds' addresses on the host
+# [HOSTI, v0, v1, ...] / [HOSTP, p0, p1, ...]: the same with the values spelled out (a pointer of 0 is NULL)
 
 # entry -> (valid argument list, positions of the sizes, positions of the REQUIRED pointers).  The valid list itself is never
 # called: every case breaks one argument of it.  Optional pointers are left NULL in the base.
@@ -67,6 +70,30 @@ INTERNAL = {
     "sn_bn_relu_forward": ([2, 8, Pp, Pp, Pp, None], [1], [2, 3, 4]),
     "sn_bn_relu_backward": ([2, 8, Pp, Pp, Pp, 0, Pp, None], [1], [2, 3, 4, 6]),
 }
+# The one-batch task evaluation (BASELINE configs[4]: every prefix of the progressive sampler as one batch), same rules.  The bases
+# hold ONE cloud / evaluation, so that the one-element host arrays above are all an entry may read; the cases past the generic ones
+# are spelled out in _task_batch_cases().
+TASK_BATCH = {
+    # B, len, C, nclouds, sizes, src, out, stream
+    "sn_cyclic_pad_cat": ([1, 8, 3, 1, HOSTI, HOSTP, Pp, None], [0, 1, 2, 3], [4, 5, 6]),
+    # B, len, C, nclouds, sizes, grad_out, grads, stream
+    "sn_cyclic_pad_cat_backward": ([1, 8, 3, 1, HOSTI, Pp, HOSTP, None], [0, 1, 2, 3], [4, 5, 6]),
+    # B, m, xyz_small, n, xyz_large, q_valid, q_group, dist_small, idx_small, dist_large, idx_large, workspace, workspace_bytes, stream
+    "sn_chamfer_forward_valid": ([2, 4, Pp, 8, Pp, Pp, 1, Pp, Pp, Pp, Pp, None, 0, None], [0, 1, 3, 6], [2, 4, 5, 7, 8, 9, 10]),
+    # B, N, y, v, twist, quat, qnorm, out, stream
+    "sn_pcrnet_head_rot_forward": ([2, 8, Pp, Pp, Pp, Pp, None, Pp, None], [0, 1], [2, 3, 4, 5, 7]),
+    # B, N, y, quat, v, grad_out, grad_twist, grad_quat, grad_qnorm, grad_v, grad_y, stream
+    "sn_pcrnet_head_rot_backward": ([2, 8, Pp, Pp, Pp, None, None, None, None, None, Pp, None], [0, 1], [2, 3, 4, 10]),
+    # R, N, group, y, v, twist, quat, qnorm, out, stream
+    "sn_pcrnet_head_rot_forward_grouped": ([4, 8, 2, Pp, Pp, Pp, Pp, None, Pp, None], [0, 1, 2], [3, 4, 5, 6, 8]),
+    # R, N, group, y, quat, v, grad_out, grad_twist, grad_quat, grad_qnorm, grad_y, stream
+    "sn_pcrnet_head_rot_backward_grouped": ([4, 8, 2, Pp, Pp, Pp, None, None, None, None, Pp, None], [0, 1, 2], [3, 4, 5, 10]),
+    # R, n1, n2, group, nev, nvalid, dist1, dist2, partial, loss, stream
+    "sn_chamfer_mean_loss_forward_grouped": ([2, 4, 8, 2, 1, HOSTI, Pp, Pp, Pp, Pp, None], [0, 1, 2, 3, 4], [5, 6, 7, 8, 9]),
+    # R, n1, xyz1, n2, xyz2, group, nev, nvalid, idx1, idx2, grad_loss, grad_xyz1, grad_xyz2, stream
+    "sn_chamfer_mean_loss_backward_grouped": ([2, 4, Pp, 8, Pp, 2, 1, HOSTI, Pp, Pp, Pp, None, None, None], [0, 1, 3, 5, 6],
+                                              [2, 4, 7, 8, 9, 10]),
+}
 # sn_skinny_linear / sn_skinny_linear2 answer a size they do not serve -- negative ones included -- with UNSUPPORTED (callers ask
 # sn_skinny_linear_supported and take another route), so the generic "negative size is a BAD argument" rule above does not fit them:
 # entry -> (valid argument list, required pointers); every case is spelled out in _skinny_cases().
@@ -79,7 +106,7 @@ SKINNY = {
 
 
 def _with(name, changes):
-    args = list((ENTRIES.get(name) or INTERNAL.get(name) or SKINNY[name])[0])
+    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or SKINNY[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -87,7 +114,7 @@ def _with(name, changes):
 
 def _cases():
     out = []  # (id, entry, args, expected code, text the message must contain | None)
-    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()):
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()):
         for pos in sizes:
             out.append(("%s-size%d-negative" % (name, pos), name, _with(name, {pos: -1}), BAD, name))
         for pos in required:
@@ -143,7 +170,7 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
-    return out + _skinny_cases() + _transform_cases(nulled)
+    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases()
 
 
 def _skinny_cases():
@@ -168,6 +195,45 @@ def _skinny_cases():
     for cid, ch in (("R0", {0: 0}), ("R257", {0: 257}), ("K0", {1: 0}), ("N0", {2: 0}), ("ksplit-0", {4: Pp, 5: 0}),
                     ("ksplit-K", {4: Pp, 5: 8}), ("ksplit-negative", {4: Pp, 5: -1})):
         out.append((wg + "-" + cid, wg, _with(wg, ch), BAD, wg))
+    return out
+
+
+def _task_batch_cases():
+    out = []
+    add = lambda cid, name, ch, text=None: out.append(("%s-%s" % (name, cid), name, _with(name, ch), BAD, text or name))
+    for name, (base, sizes, required) in TASK_BATCH.items():
+        for pos in sizes:  # (these take every size >= 1: no empty case documented)
+            add("size%d-zero" % pos, name, {pos: 0})
+    for name, ppos in (("sn_cyclic_pad_cat", 5), ("sn_cyclic_pad_cat_backward", 6)):
+        # 17 clouds: refused before either host array is read (they hold one element)
+        add("nclouds17", name, {3: 17})
+        add("a-size-of-0", name, {4: [HOSTI, 0]}, "cloud size outside [1, len]")
+        add("a-size-above-len", name, {4: [HOSTI, 9]}, "cloud size outside [1, len]")
+        add("the-second-size-above-len", name, {3: 2, 4: [HOSTI, 8, 9], ppos: [HOSTP, 4096, 4096]}, "cloud size outside [1, len]")
+    add("a-null-cloud", "sn_cyclic_pad_cat", {5: [HOSTP, 0]})  # (forward: every cloud is read; backward: NULL = no gradient wanted)
+    add("the-second-cloud-null", "sn_cyclic_pad_cat", {3: 2, 4: [HOSTI, 4, 4], 5: [HOSTP, 4096, 0]})
+    fv = "sn_chamfer_forward_valid"
+    add("n2049", fv, {3: 2049}, "2048")
+    add("m2049-n2049", fv, {1: 2049, 3: 2049}, "2048")
+    add("m-above-n", fv, {1: 9}, "m <= n")
+    add("q_group-of-0-with-B1", fv, {0: 1, 6: 0})
+    hb = "sn_pcrnet_head_rot_backward"
+    add("grad_v-without-grad_out", hb, {9: Pp}, "grad_v needs grad_out")
+    for name in ("sn_pcrnet_head_rot_forward_grouped", "sn_pcrnet_head_rot_backward_grouped"):
+        add("R-no-multiple-of-group", name, {2: 3})
+        add("group-above-R", name, {2: 8})
+    lf, lb = "sn_chamfer_mean_loss_forward_grouped", "sn_chamfer_mean_loss_backward_grouped"
+    for name, gpos in ((lf, 3), (lb, 5)):  # (R, n1 first in both; group, nev, nvalid at gpos, gpos + 1, gpos + 2)
+        add("nev17", name, {0: 34, gpos + 1: 17}, "at most 16 evaluations")  # (R = nev * group holds: the count alone is refused)
+        add("R-is-not-nev-times-group", name, {0: 3}, "R = nev * group")
+        add("R-is-not-nev-times-group-2", name, {0: 4, gpos: 2, gpos + 1: 1}, "R = nev * group")
+        add("R-no-multiple-of-group", name, {0: 3, gpos: 2, gpos + 1: 2, gpos + 2: [HOSTI, 4, 4]}, "R = nev * group")
+        add("nvalid-0", name, {gpos + 2: [HOSTI, 0]}, "valid points outside [1, n1]")
+        add("nvalid-n1-plus-1", name, {gpos + 2: [HOSTI, 5]}, "valid points outside [1, n1]")
+        add("nvalid-negative", name, {gpos + 2: [HOSTI, -1]}, "valid points outside [1, n1]")
+        add("the-last-nvalid-n1-plus-1", name, {0: 6, gpos + 1: 3, gpos + 2: [HOSTI, 4, 1, 5]}, "valid points outside [1, n1]")
+    add("n1-2049", lb, {1: 2049}, "2048")
+    add("n2-2049", lb, {3: 2049}, "2048")
     return out
 
 
@@ -197,7 +263,7 @@ def _transform_cases(nulled):
 
 
 CASES = _cases()
-IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
+IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
                                                "sn_skinny_linear_scratch_bytes"]
 
 _CHILD = r"""
@@ -206,9 +272,16 @@ sys.path.insert(0, %r)
 from samplenet_amd._lib import lib
 cases = json.load(sys.stdin)
 host = (ctypes.c_int * 1)(4)
+hostp = (ctypes.c_void_p * 1)(4096)
+def host_array(a):  # ["HOSTI", ints...] / ["HOSTP", addresses...; 0 = NULL]
+    ty = ctypes.c_int if a[0] == "HOSTI" else ctypes.c_void_p
+    return (ty * (len(a) - 1))(*[(v or None) if a[0] == "HOSTP" else v for v in a[1:]])
 res = []
 for cid, name, args, _, _ in cases:
-    conv = [ctypes.c_void_p(4096) if a == "PTR" else (ctypes.cast(host, ctypes.c_void_p) if a == "HOSTI" else a) for a in args]
+    keep = [host_array(a) if isinstance(a, list) else a for a in args]
+    conv = [ctypes.c_void_p(4096) if a == "PTR" else (ctypes.cast(host, ctypes.c_void_p) if a == "HOSTI" else
+            (ctypes.cast(hostp, ctypes.c_void_p) if a == "HOSTP" else (ctypes.cast(a, ctypes.c_void_p) if isinstance(a, ctypes.Array) else a)))
+            for a in keep]
     rc = getattr(lib, name)(*conv)
     res.append([cid, int(rc), (lib.sn_last_error_string() or b"").decode()])
 print("RESULTS " + json.dumps(res))
@@ -229,16 +302,16 @@ def results():
 def test_the_table_walks_every_entry_in_scope():
     from samplenet_amd import _lib
 
-    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()):
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()):
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto), name
         for pos, ty in enumerate(proto):
             if pos in sizes:
                 assert ty is ctypes.c_int, (name, pos)
-            if pos in required or base[pos] in (Pp, HOSTI):
+            if pos in required or base[pos] in (Pp, HOSTI, HOSTP):
                 assert ty is ctypes.c_void_p, (name, pos)
             if ty is ctypes.c_void_p:
-                assert base[pos] in (Pp, HOSTI, None), (name, pos)
+                assert base[pos] in (Pp, HOSTI, HOSTP, None), (name, pos)
     for name, (base, required) in SKINNY.items():
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto) and proto[:3] == [ctypes.c_int] * 3, name
