@@ -509,6 +509,103 @@ long long sn_adam_state_bytes(void);
 int sn_adam_update(int nchunks, const void *chunks, float *exp_avg, float *exp_avg_sq, void *state, double beta1, double beta2,
                    double eps, double weight_decay, double grad_scale, int tf_epsilon, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Training batches assembled ON THE DEVICE from an HBM-resident dataset in ONE launch (samplenet_amd/device_data.py; the reference's
+ * data side: registration/data/modelnet_loader_torch.py:114-125 ModelNetCls.__getitem__, src/pctransforms.py, src/qdataset.py:133-179
+ * QuaternionFixedDataset).  One workgroup of 256 threads per output cloud; no workgroup waits on another.  All arithmetic is fp32,
+ * one IEEE operation per operation written below (the unit is built with -ffp-contract=off), no atomics on floats.
+ *
+ * WHICH ITEM A SLOT HOLDS.  Lset = L * repeat (1 <= Lset < 2^31).  Slot b of the launch sits at the global position
+ *     g = position + rank * B + b,      epoch = g / Lset,      item = perm(seed, epoch, g mod Lset),      cloud = item mod L
+ * (order == SN_BATCH_ORDER_SEQUENTIAL: item = g mod Lset).  Batches run across epoch ends: there is no "last partial batch" -- the
+ * one difference from a DataLoader.  perm is a keyed bijection of [0, Lset): a balanced Feistel network on k bits, k the smallest
+ * EVEN number >= 2 with 2^k >= Lset, h = k / 2, mask = 2^h - 1:
+ *     (l, r) = (x >> h, x & mask);   four times, i = 0..3:  (l, r) <- (r, l ^ (F(r + rk[i]) & mask));   x' = (l << h) | r
+ *     F(v) (32-bit, wrapping):  v ^= v >> 16;  v *= 0x7FEB352D;  v ^= v >> 15;  v *= 0x846CA68B;  v ^= v >> 16
+ *     rk[0..3] = the four words of draw(index 0, stream 6, item 0, epoch)
+ * applied again while x' >= Lset (cycle walking).  A walk that starts below Lset returns below Lset after at most
+ * 2^k - Lset + 1 applications (it can pass through each of the 2^k - Lset values outside the range once), and 2^k < 4 Lset.
+ *
+ * RANDOM DRAWS.  draw(index, stream, item, epoch) = Philox4x32-10 with counter words (c0, c1, c2, c3) = (index, stream, item,
+ * epoch mod 2^32), key (k0, k1) = (seed mod 2^32, seed >> 32), multipliers M0 = 0xD2511F53 (on c0), M1 = 0xCD9E8D57 (on c2), key
+ * increments 0x9E3779B9 (k0) and 0xBB67AE85 (k1) between rounds; a round is
+ *     (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0)).
+ * The four output words are x0..x3.  A cloud's content is a function of (seed, epoch, item, dataset, recipe) alone -- not of B, of
+ * the slot, of the rank or of the step.
+ *     uniform(x)      u = (x >> 8) * 2^-24                                   in [0, 1), exact in fp32
+ *     gauss(xa, xb)   u1 = ((xa >> 8) + 1) * 2^-24, u2 = (xb >> 8) * 2^-24,  rad = sqrtf(-2 * logf(u1)),
+ *                     (s, c) = sincosf(6.28318530717958647692f * u2),        -> (rad * c, rad * s)
+ *     gauss3(x0..x3)  (g0, g1) = gauss(x0, x1), (g2, g3) = gauss(x2, x3); g0, g1, g2 are used, g3 is dropped
+ * Streams, j = the point's position in the OUTPUT cloud:
+ *     0  sort key        draw(j, 0, ..): x0 = the key of input point j (j < N)
+ *     1  jitter          draw(j, 1, ..): gauss3 -> the x, y, z offsets of output point j
+ *     2  dropout         draw(j, 2, ..): uniform(x0) = u_j
+ *     3  pair noise      draw(j, 3, ..): gauss3 -> the x, y, z noise of point j of p1
+ *     4  cloud scalars   draw(0, 4, ..): uniform(x0) scale, uniform(x1) rotation angle, uniform(x2) translation, uniform(x3) dropout ratio
+ *     5  perturbation    draw(0, 5, ..): gauss3 -> the angles about x, y, z
+ *     6  item order      draw(0, 6, 0, epoch): the Feistel round keys above
+ *
+ * PIPELINE, in this order; every stage is switched by its recipe field.  v = (x, y, z) of output point j.
+ *  1 point order   shuffle_points: the N composites (key_i << 32) | i, i < N, sorted ascending (bitonic sort in LDS, padded to a power
+ *                  of two with all-ones sentinels; composites are distinct: no tie rule); output point j is input point
+ *                  (composite_j mod 2^32) of the cloud's first N points.  Off: output point j is input point j.  N <= 2048 with the
+ *                  shuffle, any N <= P without; else SN_ERR_UNSUPPORTED.
+ *  2 unit_cube     per axis lo_c = min, hi_c = max over the N points, e_c = hi_c - lo_c, s = max(e_x, e_y, e_z); v_c = v_c / s;
+ *                  m_c = (sum over the points of v_c) / (float)N; v_c = v_c - m_c  (pctransforms.py:162-166).  The sums have one
+ *                  fixed order: thread t adds positions t, t + 256, .. ascending, the 64 lanes of a wave combine by the xor tree
+ *                  (offsets 32, 16, .. 1), the four wave sums are added in ascending order.  s == 0 divides by zero like the reference.
+ *  3 scale         f = scale_lo + u * (scale_hi - scale_lo);  v_c = v_c * f
+ *  4 rotate        (s, c) = sincosf(u * 6.28318530717958647692f), a = the unit axis (normalised on the host in fp64, rounded to fp32),
+ *                  t = 1 - c,  R[i][j] = (c * [i == j] + s * K[i][j]) + (t * a_i) * a_j  with K = [[0,-az,ay],[az,0,-ax],[-ay,ax,0]];
+ *                  v_i = (R[i][0] x + R[i][1] y) + R[i][2] z   (pctransforms.py:12-42, 59-65)
+ *  5 perturb       angle_k = min(max(perturb_sigma * g_k, -perturb_clip), perturb_clip), k = x, y, z; Rz Ry Rx applied as three plane
+ *                  rotations, about x first: (y, z) <- (c y - s z, s y + c z); about y: (x, z) <- (c x + s z, c z - s x); about z:
+ *                  (x, y) <- (c x - s y, s x + c y)   (pctransforms.py:75-96)
+ *  6 translate     d = u * (translate_range + translate_range) - translate_range;  v_c = v_c + d  (ONE scalar on all three axes:
+ *                  what pctransforms.py:120-127 does)
+ *  7 jitter        v_c = v_c + min(max(jitter_std * g_c, -jitter_clip), jitter_clip)
+ *  8 dropout       ratio = u * dropout_max;  every point with u_j <= ratio becomes output point 0 (as it stands after stage 7)
+ *  9 pair          p1_j = qrot(pair_quat[item], p0_j) with sn_qrot_forward's expression; pair_noise: + pair_noise_std * g_c
+ * p0 is the cloud after stage 8.
+ *
+ * STATE.  `state`: sn_batch_state_bytes() = 64 bytes on the device, 8-byte aligned: { long long position; unsigned arrivals (zero
+ * between launches); padding }.  position < 0: every workgroup reads the block's position first, then counts itself as arrived; the
+ * LAST to arrive clears the count and adds B * world to the position -- nothing spins, and a replayed graph yields successive
+ * batches with no host write.  position >= 0: that position is used and the block is neither read nor written (may be NULL).
+ *
+ * Arguments: points (L, P, 3) fp32 and labels (L) int64 (needed when out_labels != NULL): the resident set; recipe: HOST memory,
+ * read during the call; pair_quat (Lset, 4) as (w, x, y, z), needed for p1 / igt.  Outputs (caller-owned): p0 (B, N, 3) or
+ * (B, 3, N) by `layout`; optional p1 (same shape), out_labels (B) int64, igt (B, 7) = the item's quaternion and three zeros,
+ * items (B) int32.  Checked on the host before any device work: negative B / N / P / L / repeat < 1, N > P, rank outside [0, world),
+ * scale_lo > scale_hi, a negative clip / std / range, dropout_max outside [0, 1), a zero rotation axis, a bad layout or order
+ * selector, a NULL required pointer -> SN_ERR_BAD_ARGUMENT.  B == 0 is a no-op that succeeds. */
+#define SN_BATCH_ORDER_SHUFFLED 0
+#define SN_BATCH_ORDER_SEQUENTIAL 1
+typedef struct sn_batch_recipe {
+    int order;          /* SN_BATCH_ORDER_* */
+    int shuffle_points; /* stage 1 */
+    int unit_cube;      /* stage 2 */
+    int scale;          /* stage 3 */
+    float scale_lo, scale_hi;
+    int rotate;         /* stage 4 */
+    float axis[3];
+    int perturb;        /* stage 5 */
+    float perturb_sigma, perturb_clip;
+    int translate;      /* stage 6 */
+    float translate_range;
+    int jitter;         /* stage 7 */
+    float jitter_std, jitter_clip;
+    int dropout;        /* stage 8 */
+    float dropout_max;
+    int pair_noise;     /* stage 9: noise on p1 */
+    float pair_noise_std;
+} sn_batch_recipe;
+long long sn_batch_state_bytes(void);
+int sn_batch_assemble(int B, int N, int P, int L, int repeat, const float *points, const long long *labels,
+                      const sn_batch_recipe *recipe, unsigned long long seed, int rank, int world, long long position, void *state,
+                      const float *pair_quat, int layout, float *p0, float *p1, long long *out_labels, float *igt, int *items,
+                      sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ is missing -- there is no CPU or eager-PyTorch fallback.
 from . import _lib  # noqa: F401  (loads the HIP library or raises)
 from . import ops, optim, sputils  # noqa: F401
 from .autoencoder import PointNetAE, reconstruction_loss  # noqa: F401
+from .device_data import BatchRecipe, DeviceBatchSource, DeviceCloudSet  # noqa: F401
 from .classifier import PointNetCls, PointNetClsBasic, classification_loss  # noqa: F401
 from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: F401
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
@@ -17,4 +18,4 @@ from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
            "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
-           "sputils", "ops", "optim"]
+           "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet"]

@@ -166,11 +166,15 @@ PROTOTYPES = {
     "sn_adam_state_bytes": [],
     "sn_adam_update": [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                        ctypes.c_double, _i, _vp],
+    "sn_batch_state_bytes": [],
+    "sn_batch_assemble": [_i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _i, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp,
+                          _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"sn_last_error_string": ctypes.c_char_p, "sn_workspace_bytes": ctypes.c_longlong,
              "sn_pairscan_workspace_bytes": ctypes.c_longlong, "sn_linear_forward_maxpool_wide_scratch_bytes": ctypes.c_longlong,
              "sn_skinny_linear_scratch_bytes": ctypes.c_longlong,
              "sn_adam_state_bytes": ctypes.c_longlong,
+             "sn_batch_state_bytes": ctypes.c_longlong,
              "sn_layer_backward_in3_stats_floats": ctypes.c_longlong,
              "sn_conv_stack_acc_elems": ctypes.c_longlong,
              "sn_conv_stack_acc_sum_elems": ctypes.c_longlong,

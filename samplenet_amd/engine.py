@@ -17,8 +17,20 @@ import torch
 class SamplerTrainStep:
     def __init__(self, net, example_x, alpha=0.01, lmbda=0.01, gamma=1.0, delta=0.0, task_loss=None, reducer=None,
                  use_graph=True, warmup=3, fused_loss=True, input_ring=None, fused_head=True, overlap_allreduce=None,
-                 allreduce="graph", optimizer=None):
+                 allreduce="graph", optimizer=None, input_source=None):
         self.net, self.reducer = net, reducer
+        # input_source: a samplenet_amd.device_data.DeviceBatchSource of example_x's shape -- its one launch into self.x is the FIRST
+        # node of the step's graph (issued eagerly in front of the step with use_graph=False): step() takes no batch and the host
+        # touches nothing.  A source that makes pairs fills a second target, self.x1, and the task loss is called as
+        # task_loss(proj, x1).  The warm-up passes run on example_x and draw nothing from the source.
+        if input_source is not None:
+            if input_ring is not None:
+                raise ValueError("input_source and input_ring are mutually exclusive")
+            if tuple(input_source.shape()) != tuple(example_x.shape) or input_source.device != example_x.device:
+                raise ValueError("input_source makes %s batches on %s, example_x is %s on %s"
+                                 % (tuple(input_source.shape()), input_source.device, tuple(example_x.shape), example_x.device))
+        self.source = input_source
+        self.x1 = None
         # optimizer: a samplenet_amd.optim.Adam over the net's parameters -- its update (one launch per parameter group) is issued
         # right behind reducer.reduce(): as the last node(s) of the step's graph where the gradients are final inside it (no
         # collective, or allreduce 'graph' / 'graph-fork'), behind the Python-side collective otherwise ('after', the split step),
@@ -49,6 +61,10 @@ class SamplerTrainStep:
             use_graph = False
         self.use_graph = bool(use_graph)
         self.x = example_x.clone() if self.ring is None else self.ring[0]
+        if self.source is not None and self.source.makes_pairs:
+            self.x1 = example_x.clone()
+            if task_loss is not None:
+                self.task_loss = lambda proj, _f=task_loss: _f(proj, self.x1)
         self._one = torch.ones((), device=example_x.device, dtype=torch.float32)
         self.graph = None
         self.loss = None
@@ -101,6 +117,7 @@ class SamplerTrainStep:
         # the step is being constructed (chosen over snapshotting parameters, moments and the state block: nothing to restore, and
         # the update is the same node behind every placement, so it does not change which one wins).
         optimizer, self.optimizer = self.optimizer, None
+        source, self.source = self.source, None  # (likewise: the probes' replays must not draw batches)
         for mode in ("graph", "after", "graph-fork"):
             self.allreduce, self.in_graph = mode, mode != "after"
             self._ring_graphs, self._ring_loss, self._ring_outputs = [], [], []
@@ -147,7 +164,7 @@ class SamplerTrainStep:
         self.allreduce_probe = {"ms_per_step": dict(zip(("graph", "after", "graph-fork"), vals)), "chosen": best, "replays": replays}
         self.allreduce, self.in_graph = best, best != "after"
         self._ring_graphs, self._ring_loss, self._ring_outputs = [], [], []
-        self.optimizer = optimizer
+        self.optimizer, self.source = optimizer, source
         self._capture(1)
 
     def _probe_step(self):
@@ -301,6 +318,7 @@ class SamplerTrainStep:
                 #  a query of an event whose stream is capturing, and the watchdog aborts the process)
                 kw = {} if (self.reducer is not None and self.reducer.collective) else {"stream": self._cap_stream}
                 with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local", **kw):
+                    self._pull()  # captured: the batch is assembled by the replay itself
                     loss = self._step()
                     if self.in_graph:
                         self.reducer.reduce()  # captured: the collective(s) replay with the step
@@ -327,6 +345,7 @@ class SamplerTrainStep:
         with torch.cuda.stream(cap), torch.no_grad():
             graphs[0].capture_begin(pool=pool, capture_error_mode="thread_local")
             try:
+                self._pull()
                 loss = self._step(boundary)
             finally:
                 graphs[-1].capture_end()
@@ -394,6 +413,17 @@ class SamplerTrainStep:
         # for as long as the graphs, whatever happens to the module's own list
         self._plan_refs = list(self.net.__dict__.get("_sn_plans", ()))
 
+    def _pull(self):
+        """input_source: the next batch into the step's static input(s) -- one launch on the current stream."""
+        if self.source is not None:
+            self.source.next_into(self.x, self.x1)
+
+    def step(self):
+        """One step on the next batch of input_source; returns the (static) loss tensor."""
+        if self.source is None:
+            raise RuntimeError("step() needs an input_source; call the step with a batch instead")
+        return self._run()
+
     def _update_in_graph(self):
         """The update is a node of the step's graph when nothing has to run between the graph and it: no collective at all, or the
         collective inside the graph.  (Behind the Python-side collective of 'after' and behind graph 2 of the split step it is a
@@ -450,12 +480,18 @@ class SamplerTrainStep:
         Gradients are in p.grad afterwards (cross-rank averaged when a reducer is attached)."""
         if self.ring is not None:
             raise RuntimeError("this step was built on an input ring: fill input_ring[i] in place and call replay(i)")
+        if self.source is not None:
+            raise RuntimeError("this step was built on an input source: call step()")
         self.x.copy_(x, non_blocking=True)
+        return self._run()
+
+    def _run(self):
         if self._ring_graphs:
             if self.optimizer is not None:
                 self.optimizer._sync_lr()  # (the host side of step(): the table cannot move under a captured step)
             self._replay_graphs(0)
         else:
+            self._pull()
             self.loss = self._step()
         if self.reducer is not None:
             self.reducer.reduce(collective=not (self.in_graph and self._ring_graphs), replayed=bool(self._ring_graphs))
