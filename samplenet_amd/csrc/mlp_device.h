@@ -1088,6 +1088,58 @@ __device__ __forceinline__ bool partial_sums(int nblk, int C, const float *__res
     return partial_sums_in(red, red2, nblk, C, stats, cblock, s0, s1, 0);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Raw buffer stores with a compile-time cache policy.  resource (SGPRs) + per-lane byte offset (VGPR) + wave-uniform byte offset
+// (SGPR); stores beyond num_records are dropped.  AUX is the instruction's cache-policy field and reaches the builtin as a constant:
+//   0 default (write-back: the line stays dirty in the XCD's L2 until a release writes it back), 16 sc1 (write-through: the bytes
+//   leave the L2 as they are stored and the line is dropped), 2 nt (stays in the L2, marked for early eviction), 18 both.
+// A policy changes where and when the bytes travel, never their value.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __amdgpu_buffer_rsrc_t sn_rsrc;
+__device__ __forceinline__ sn_rsrc make_rsrc(const void *p, unsigned bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
+}
+template <int AUX = 0>
+__device__ __forceinline__ void buf_store4(const float4 &v, sn_rsrc r, unsigned voff, unsigned soff)
+{
+    static_assert(AUX == 0 || AUX == 2 || AUX == 16 || AUX == 18, "cache policy: 0, nt (2), sc1 (16) or both");
+    u32x4 x;
+    x.x = __float_as_uint(v.x), x.y = __float_as_uint(v.y), x.z = __float_as_uint(v.z), x.w = __float_as_uint(v.w);
+    __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, AUX);
+}
+template <int AUX = 0>
+__device__ __forceinline__ void buf_store1(float v, sn_rsrc r, unsigned voff, unsigned soff)
+{
+    static_assert(AUX == 0 || AUX == 2 || AUX == 16 || AUX == 18, "cache policy: 0, nt (2), sc1 (16) or both");
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, AUX);
+}
+
+// The conv stack's bulk outputs -- written once per step, never re-read by the kernel that writes them -- by store family.  With the
+// default policy a kernel ends with its whole output dirty in the XCDs' L2s (8-34 MB per kernel at B = 32) and the write-back
+// happens in the end-of-kernel release, with nothing left to overlap it; written through, the bytes leave while the kernel still
+// computes.  Measured at the headline's batch, rocprofv3 kernel traces on one box, avg us per launch, each family judged on its
+// writer kernels PLUS the kernel that reads what it writes (profiles/stores/families.txt; run-to-run spread of a sum 0.3-1.1 us):
+//   SN_ST_Z     four forward GEMMs                           0: 42.0   16: 37.1   2: 41.0   18: 40.1
+//   SN_ST_DY    four backward GEMMs                          0: 57.0   16: 56.4   2: 57.1   18: 56.9   (alone: inside the spread)
+//   SN_ST_PART  four backward GEMMs + post_bwd_in3_kernel    0: 65.8   16: 64.9   2: 69.7   18: 69.3   (nt: the reader 8.8 -> 13.3)
+//   DY = 16 AND PART = 16                                    63.1  -- the two families share their kernels: while one of them is still
+//     write-back the closing release still has dirty lines to write back, with both written through it has none (DY = 2 beside
+//     PART = 16: 64.8, nothing)
+//   all three at 16: the nine kernels 107.8 -> 100.2 us, the step 0.1812 -> 0.1743 ms (profiles/stores/headline_ab.txt).  B = 512 / 2048,
+//   where a workgroup walks many tiles and the write-back was spread over the kernel already: 1.152-1.159 -> 1.149-1.156 ms and
+//   3.990-4.026 -> 4.007-4.013 ms, inside the spread (batch_sweep_ab.txt) -- one policy for every shape, no second instantiation.
+#ifndef SN_ST_Z
+#define SN_ST_Z 16    // forward Z tiles: linear_fwd_kernel (FULL tiles), linear_fwd_persist_kernel, conv_in3_fwd_kernel
+#endif
+#ifndef SN_ST_DY
+#define SN_ST_DY 16   // backward dYprev tiles of conv_bwd_bx3_kernel (store_prev, the tail store, the DM = 1 raw sum)
+#endif
+#ifndef SN_ST_PART
+#define SN_ST_PART 16 // conv_bwd_bx3_kernel's closing burst: weight-gradient partials (64 KB per workgroup at 128 x 128), statistics partials
+#endif
+
 }  // namespace sn
 
 #ifdef SN_TIMELINE

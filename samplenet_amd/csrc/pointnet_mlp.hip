@@ -237,12 +237,14 @@ __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu
                 }
             }
             if (FULL && store_z) {
-                float *zt = g.z + (size_t)(row0 + (wr * T::TM + i) * 32) * Co + col0 + (wc * T::TN + j) * 32 + (lane & 7) * 4;
+                // the tile's BM rows of Z as a buffer: a per-lane offset that never changes + the fragment's offset (SN_ST_Z)
+                const sn_rsrc zt = make_rsrc(g.z + (size_t)row0 * Co, (unsigned)(T::BM * Co) * 4);
+                const unsigned zvo = (unsigned)((lane >> 3) * Co + (lane & 7) * 4) * 4;
+                const unsigned zso = (unsigned)((wr * T::TM + i) * 32 * Co + col0 + (wc * T::TN + j) * 32) * 4;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int rt = 8 * q + (lane >> 3);
-                    *reinterpret_cast<float4 *>(zt + (size_t)rt * Co) =
-                        *reinterpret_cast<const float4 *>(Ts + rt * 36 + (lane & 7) * 4);
+                    buf_store4<SN_ST_Z>(*reinterpret_cast<const float4 *>(Ts + rt * 36 + (lane & 7) * 4), zt, zvo, zso + (unsigned)(8 * q * Co) * 4);
                 }
             }
         }
@@ -569,11 +571,13 @@ __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu
                 if (v < pmin) pmin = v, imin = row;
             }
             if (g.z && SN_FWDP_ABL != 3) {
-                float *zt = g.z + (size_t)(row0 + wr * 32 + 16 * hf) * Co + wc * 32 + (lane & 7) * 4;
+                const sn_rsrc zt = make_rsrc(g.z + (size_t)row0 * Co, (unsigned)(T::BM * Co) * 4);  // (this tile's rows; SN_ST_Z)
+                const unsigned zvo = (unsigned)((lane >> 3) * Co + (lane & 7) * 4) * 4;
+                const unsigned zso = (unsigned)((wr * 32 + 16 * hf) * Co + wc * 32) * 4;
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int rt = 8 * q + (lane >> 3);
-                    *reinterpret_cast<float4 *>(zt + (size_t)rt * Co) = *reinterpret_cast<const float4 *>(Ts + rt * 36 + (lane & 7) * 4);
+                    buf_store4<SN_ST_Z>(*reinterpret_cast<const float4 *>(Ts + rt * 36 + (lane & 7) * 4), zt, zvo, zso + (unsigned)(8 * q * Co) * 4);
                 }
             }
         }
@@ -1143,8 +1147,9 @@ __global__ void __launch_bounds__(256) conv_in3_fwd_kernel(int R, int Co, const 
                 s1[j] += v[j] * v[j];
             }
             if (r < R && z) {  // (z == NULL: statistics only -- the consumers rebuild the activation from the cloud, FwdArgs::x3)
-                if (vec) {
-                    *reinterpret_cast<float4 *>(z + (size_t)r * Co + co) = make_float4(v[0], v[1], v[2], v[3]);
+                if (vec) {  // (the block's 64 rows of Z as a buffer; SN_ST_Z)
+                    buf_store4<SN_ST_Z>(make_float4(v[0], v[1], v[2], v[3]), make_rsrc(z + (size_t)row0 * Co, (unsigned)(min(64, R - row0) * Co) * 4),
+                                        (unsigned)((rs + 16 * i) * Co + co) * 4, 0u);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)

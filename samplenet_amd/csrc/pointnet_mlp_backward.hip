@@ -228,12 +228,7 @@ struct ConvBwdArgs {
 // VALU instructions of this wave only find an issue slot now and then: with flat addressing the 64-bit per-lane address
 // arithmetic in front of ~30 memory instructions made the top of every iteration take 2 us.  Out-of-range rows need no
 // special casing either: loads beyond num_records return 0, stores are dropped.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t sn_rsrc;
-__device__ __forceinline__ sn_rsrc make_rsrc(const void *p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
-}
+// (make_rsrc / buf_store4 and the stores' cache policy: mlp_device.h)
 __device__ __forceinline__ float4 buf_load4(sn_rsrc r, unsigned voff, unsigned soff)
 {
     const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
@@ -253,12 +248,6 @@ __device__ __forceinline__ int4 buf_load4i(sn_rsrc r, unsigned voff, unsigned so
 __device__ __forceinline__ float buf_load1(sn_rsrc r, unsigned voff, unsigned soff)
 {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void buf_store4(const float4 &v, sn_rsrc r, unsigned voff, unsigned soff)
-{
-    u32x4 x;
-    x.x = __float_as_uint(v.x), x.y = __float_as_uint(v.y), x.z = __float_as_uint(v.z), x.w = __float_as_uint(v.w);
-    __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, 0);
 }
 
 struct CbfRsrc {
@@ -1040,7 +1029,7 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
                 if (!IN3 && it > 0 && kh == 0 && SN_CBX_ABL != 3) {
                     const unsigned oso = (unsigned)(tile - tst) * (TR * GP * 4);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) buf_store4(vout[i], rs.dyprev, ovo, oso + i * (8 * GP * 4));
+                    for (int i = 0; i < 4; ++i) buf_store4<SN_ST_DY>(vout[i], rs.dyprev, ovo, oso + i * (8 * GP * 4));
                 }
             };
             if (!SN_CBX_LATE_ST || SN_CBX_ABL == 1) store_prev();
@@ -1193,7 +1182,7 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         if (!IN3 && tile != tile0 && kh == 0) {
             const unsigned oso = (unsigned)(tile - tst) * (TR * GP * 4);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) buf_store4(vout[i], rs.dyprev, ovo, oso + i * (8 * GP * 4));
+            for (int i = 0; i < 4; ++i) buf_store4<SN_ST_DY>(vout[i], rs.dyprev, ovo, oso + i * (8 * GP * 4));
         }
         float *red = lds;  // [RB][NST][CI]   (every wave is past its last LDS read: barrier at the end of the loop)
         const float t0 = s0 + __shfl_xor(s0, 32), t1 = s1 + __shfl_xor(s1, 32);
@@ -1366,7 +1355,10 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         }
         SN_TL(6);
         const int pld = g.part_ld > 0 ? g.part_ld : CI;
-        float *P = g.part + (size_t)blockIdx.x * (g.part_wg_stride > 0 ? g.part_wg_stride : CO * CI);
+        // this workgroup's [CO][CI] block (row pitch pld): one burst after the last tile, read next by another kernel (SN_ST_PART)
+        const float *P = g.part + (size_t)blockIdx.x * (g.part_wg_stride > 0 ? g.part_wg_stride : CO * CI);
+        const sn_rsrc rpart = make_rsrc(P, (unsigned)((CO - 1) * pld + CI) * 4);
+        const unsigned wvo = ((lane >> 3) * pld + (lane & 7) * 4) * 4;
         float *Tw = lds + RB * NST * CI + 16 + (wave - 4) * (32 * 36);  // behind the dgrad waves' statistics area
 #pragma unroll
         for (int n = 0; n < NWT; ++n) {
@@ -1376,8 +1368,8 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int rt = 8 * i + (lane >> 3);
-                *reinterpret_cast<float4 *>(P + (size_t)(cob * 32 + rt) * pld + colb + (lane & 7) * 4) =
-                    *reinterpret_cast<const float4 *>(Tw + rt * 36 + (lane & 7) * 4);
+                buf_store4<SN_ST_PART>(*reinterpret_cast<const float4 *>(Tw + rt * 36 + (lane & 7) * 4), rpart, wvo,
+                                       (unsigned)((cob * 32 + 8 * i) * pld + colb) * 4);
             }
         }
     }
@@ -1385,7 +1377,8 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
     if (tid < CI && DM != 1) {
         const float *red = lds;
         const int sld = g.stats_ld > 0 ? g.stats_ld : CI;
-        float *st = g.stats + (size_t)blockIdx.x * (IN3 ? 6 : 2) * sld;
+        // (the statistics partials leave with the weight-gradient partials' policy: the same burst, the same reader)
+        const sn_rsrc rst = make_rsrc(g.stats + (size_t)blockIdx.x * (IN3 ? 6 : 2) * sld, (unsigned)(IN3 ? 6 : 2) * sld * 4);
 #pragma unroll
         for (int k = 0; k < NST; ++k) {
             float a = red[k * CI + tid];
@@ -1393,9 +1386,9 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             if (!IN3 && g.acc_out)
                 fx_add<kFxShiftBwd>(g.acc_out, blockIdx.x % kFxSlots, k, tid, a);
             else
-                st[k * sld + tid] = a;
+                buf_store1<SN_ST_PART>(a, rst, (unsigned)tid * 4, (unsigned)(k * sld) * 4);
         }
-        if (IN3) st[5 * CI + tid] = tid < 9 ? red[RB * NST * CI + tid] : 0.f;
+        if (IN3) buf_store1<SN_ST_PART>(tid < 9 ? red[RB * NST * CI + tid] : 0.f, rst, (unsigned)tid * 4, (unsigned)(5 * CI) * 4);
     }
     SN_TL_DRAIN();
     SN_TL(7);
