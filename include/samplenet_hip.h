@@ -269,6 +269,9 @@ int sn_weighted_gather_backward_ordered(int b, int c, int n, int m, int k, const
  * vectors of all 10 levels are kept so that `match` is written once instead of being
  * read-modify-written per level.  sn_matchcost needs sn_workspace_bytes("matchcost", ...) bytes
  * of scratch for its per-workgroup partial sums (deterministic two-stage reduction).
+ * grad1 / grad2 may each be NULL: the other is computed alone.  An empty cloud (n == 0 or m == 0,
+ * b > 0) makes the cost the constant zero: sn_matchcost zeroes cost, sn_matchcost_grad zeroes every
+ * gradient buffer given (on the call's stream), sn_approxmatch has nothing to write.
  * ------------------------------------------------------------------------------------------- */
 int sn_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match,
                    float *temp, sn_stream_t stream);
@@ -281,7 +284,9 @@ int sn_matchcost_grad(int b, int n, int m, const float *xyz1, const float *xyz2,
  * gradient of each cost w.r.t. its clouds with match held constant (tf_approxmatch.py:54-64).  match[l,k] is re-evaluated
  * from the per-level ratio vectors inside the sweeps: 839 MB never written at B = 50, 2048 x 2048.  cost and grad1 are
  * bit-identical to sn_matchcost / sn_matchcost_grad on the materialised match; grad2 sums in a different order (1e-5).
- * temp: sn_workspace_bytes("emd_loss", b, n, m, 0) bytes. */
+ * temp: sn_workspace_bytes("emd_loss", b, n, m, 0) bytes, 16-byte aligned (the tile partials of the one-sweep form are float4
+ * accesses at a 16-byte offset from it; any other alignment is SN_ERR_BAD_ARGUMENT).  grad1 / grad2 may each be NULL.
+ * n == 0 or m == 0 (b > 0): cost and every gradient buffer given are zeroed on the call's stream. */
 int sn_emd_loss(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *grad1, float *grad2,
                 float *temp, sn_stream_t stream);
 

@@ -16,6 +16,7 @@
 //     streaming kernel -- the same terms added in the same order as the reference's `+=`, so the
 //     result is identical, at 1/20 of the HBM traffic (write-once instead of 10 x read+write).
 #include <algorithm>
+#include <cstdint>
 
 #include "sn_common.h"
 
@@ -710,6 +711,10 @@ using namespace sn;
 // multiple of 64 points, at most one per 256 points of the other cloud
 static void emd_seg_plan(int b, int nself, int nother, int &nseg, int &len)
 {
+    if (nother <= 0) {  // an empty cloud: nothing to cut (sn_workspace_bytes is asked for such shapes too)
+        nseg = 1, len = 0;
+        return;
+    }
     const long long base = (long long)b * ((nself + 255) / 256);
     long long s = base > 0 ? (2048 + base - 1) / base : 1;
     s = std::max<long long>(1, std::min<long long>(s, nother / 256));
@@ -735,6 +740,15 @@ long long sn_emd_sweep2d_floats(int b, int n, int m)
     const long long nkt = (n + kT2 - 1) / kT2, nlt = (m + kT2 - 1) / kT2;
     return (long long)b * (nlt * n * 4 + nkt * m * 3);
 }
+// where those tile partials start: behind the level workspace and the b * ceil(n / 256) cost partials, rounded up to 4 floats -- P1 is
+// written and read as float4, and `temp` itself is 16-byte aligned by contract (include/samplenet_hip.h)
+long long sn_emd_sweep2d_offset_floats(int b, int n, int m)
+{
+    const long long front = sn_emd_workspace_floats(b, n, m) + (long long)b * ((n + 255) / 256);
+    return (front + 3) / 4 * 4;
+}
+// sn_workspace_bytes("emd_loss") / 4: level vectors | segment partials, counters | cost partials | pad | P1 | P2
+long long sn_emd_loss_floats(int b, int n, int m) { return sn_emd_sweep2d_offset_floats(b, n, m) + sn_emd_sweep2d_floats(b, n, m); }
 // test / A-B hook: 0 = the level passes sweep the whole other cloud per workgroup (the one-range form of rounds 1-5), 1 (default) =
 // segmented level passes (EmdSeg) where the shape makes more than one range
 static int g_emd_segments = 1;
@@ -753,12 +767,22 @@ extern "C" int sn_emd_set_sweep2d(int on)
     return prev;
 }
 
-template <bool FAST>
-static int emd_auction(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, sn_stream_t stream)
+// an empty cloud on either side: the cost is the constant 0, so every gradient buffer given is zero (on the call's stream)
+static int emd_zero_grads(int b, int n, int m, float *grad1, float *grad2, hipStream_t st, const char *who)
 {
-    SN_REQUIRE(b >= 0 && n >= 0 && m >= 0, "negative size");
+    hipError_t e = hipSuccess;
+    if (grad1 && n > 0) e = hipMemsetAsync(grad1, 0, sizeof(float) * 3 * (size_t)b * n, st);
+    if (e == hipSuccess && grad2 && m > 0) e = hipMemsetAsync(grad2, 0, sizeof(float) * 3 * (size_t)b * m, st);
+    return e == hipSuccess ? 0 : sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
+}
+
+template <bool FAST>
+static int emd_auction(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp, sn_stream_t stream,
+                       const char *who)
+{
+    SN_REQUIRE_AS(who, b >= 0 && n >= 0 && m >= 0, "negative size");
     if (b == 0 || n == 0 || m == 0) return 0;
-    SN_REQUIRE(xyz1 && xyz2 && temp, "null pointer");
+    SN_REQUIRE_AS(who, xyz1 && xyz2 && temp, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     float multiL, multiR;  // tf_approxmatch_g.cu:3-10 (integer division)
     if (n >= m)
@@ -777,7 +801,7 @@ static int emd_auction(int b, int n, int m, const float *xyz1, const float *xyz2
         sk.counter = sl.counter = reinterpret_cast<unsigned *>(segbase + psum);
         // (the workspace is the caller's and arrives uninitialised: the counters start at zero; every launch leaves them zero)
         hipError_t e = hipMemsetAsync(sk.counter, 0, sizeof(unsigned) * (size_t)nctr, st);
-        if (e != hipSuccess) return sn_set_error((int)e, "emd: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
     }
     const dim3 gk((n + 255) / 256, b, sk.nseg), gl((m + 255) / 256, b, sl.nseg);
     for (int li = 0; li < kLevels; ++li) {
@@ -787,14 +811,14 @@ static int emd_auction(int b, int n, int m, const float *xyz1, const float *xyz2
     if (match)
         hipLaunchKernelGGL(emd_materialize_kernel, dim3((n + 255) / 256, (m + 15) / 16, b), dim3(256), 0, st, n, m,
                            xyz1, xyz2, temp, match);
-    SN_LAUNCH_CHECK();
+    SN_LAUNCH_CHECK_AS(who);
     return 0;
 }
 
 extern "C" int sn_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, float *temp,
                               sn_stream_t stream)
 {
-    return emd_auction<false>(b, n, m, xyz1, xyz2, match, temp, stream);
+    return emd_auction<false>(b, n, m, xyz1, xyz2, match, temp, stream, "sn_approxmatch");
 }
 
 extern "C" int sn_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
@@ -820,9 +844,10 @@ extern "C" int sn_matchcost_grad(int b, int n, int m, const float *xyz1, const f
                                  float *grad1, float *grad2, sn_stream_t stream)
 {
     SN_REQUIRE(b >= 0 && n >= 0 && m >= 0, "negative size");
-    if (b == 0 || n == 0 || m == 0) return 0;
-    SN_REQUIRE(xyz1 && xyz2 && match, "null pointer");
+    if (b == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || m == 0) return emd_zero_grads(b, n, m, grad1, grad2, st, "sn_matchcost_grad");
+    SN_REQUIRE(xyz1 && xyz2 && match, "null pointer");
     if (grad1) hipLaunchKernelGGL(emd_grad1_kernel, dim3((n + 255) / 256, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, grad1);
     if (grad2) hipLaunchKernelGGL(emd_grad2_kernel, dim3((m + 3) / 4, b), dim3(256), 0, st, n, m, xyz1, xyz2, match, grad2);
     SN_LAUNCH_CHECK();
@@ -830,7 +855,7 @@ extern "C" int sn_matchcost_grad(int b, int n, int m, const float *xyz1, const f
 }
 
 // cost (b) = match_cost(approx_match(xyz1, xyz2)) and its gradients without materialising match (see emd_loss_sweep_kernel).
-// temp: sn_workspace_bytes("emd_loss", b, n, m, 0) bytes.  grad1 / grad2 may be NULL.
+// temp: sn_workspace_bytes("emd_loss", b, n, m, 0) bytes, 16-byte aligned.  grad1 / grad2 may be NULL.
 template <bool FAST>
 static int emd_loss_impl(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *grad1, float *grad2,
                          float *temp, sn_stream_t stream, const char *who)
@@ -841,22 +866,24 @@ static int emd_loss_impl(int b, int n, int m, const float *xyz1, const float *xy
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 || m == 0) {
         hipError_t e = hipMemsetAsync(cost, 0, sizeof(float) * b, st);
-        return e == hipSuccess ? 0 : sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
+        if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", who, hipGetErrorString(e));
+        return emd_zero_grads(b, n, m, grad1, grad2, st, who);
     }
     if (!(xyz1 && xyz2 && temp)) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: null pointer", who);
-    int rc = emd_auction<FAST>(b, n, m, xyz1, xyz2, nullptr, temp, stream);  // the 20 level passes; no materialisation
+    if (reinterpret_cast<uintptr_t>(temp) % 16) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: temp not 16-byte aligned", who);
+    int rc = emd_auction<FAST>(b, n, m, xyz1, xyz2, nullptr, temp, stream, who);  // the 20 level passes; no materialisation
     if (rc) return rc;
     float *partial = temp + sn_emd_workspace_floats(b, n, m);
     const int nparts = (n + 255) / 256;
     if (FAST && g_emd_sweep2d) {
         // the default loss form: every pair's match value evaluated once for cost, grad1 and grad2 (see emd_loss_sweep2d_kernel)
         const int nkt = (n + kT2 - 1) / kT2, nlt = (m + kT2 - 1) / kT2;
-        float *P1 = partial + (size_t)b * nparts, *P2 = P1 + (size_t)b * nlt * n * 4;
+        float *P1 = temp + sn_emd_sweep2d_offset_floats(b, n, m), *P2 = P1 + (size_t)b * nlt * n * 4;  // (P1: a multiple of 4 floats from temp)
         hipLaunchKernelGGL((emd_loss_sweep2d_kernel<FAST>), dim3(nkt, nlt, b), dim3(256), 0, st, n, m, xyz1, xyz2, temp, P1, P2);
         hipLaunchKernelGGL(emd_loss_reduce2d_kernel, dim3((std::max(n, m) + 255) / 256, b), dim3(256), 0, st, n, m, nkt, nlt, P1, P2, partial,
                            grad1, grad2);
         hipLaunchKernelGGL(emd_cost_final_kernel, dim3((b + 255) / 256), dim3(256), 0, st, b, nparts, partial, cost);
-        SN_LAUNCH_CHECK();
+        SN_LAUNCH_CHECK_AS(who);
         return 0;
     }
     hipLaunchKernelGGL((emd_loss_sweep_kernel<true, FAST>), dim3(nparts, b), dim3(256), 0, st, n, m, xyz1, xyz2, temp, partial, grad1);
@@ -864,7 +891,7 @@ static int emd_loss_impl(int b, int n, int m, const float *xyz1, const float *xy
     if (grad2)
         hipLaunchKernelGGL((emd_loss_sweep_kernel<false, FAST>), dim3((m + 255) / 256, b), dim3(256), 0, st, n, m, xyz1, xyz2, temp,
                            (float *)nullptr, grad2);
-    SN_LAUNCH_CHECK();
+    SN_LAUNCH_CHECK_AS(who);
     return 0;
 }
 
