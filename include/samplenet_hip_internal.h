@@ -396,6 +396,31 @@ int sn_pcrnet_head_rot_backward(int B, int N, const float *y, const float *quat,
                                 const float *grad_twist, const float *grad_quat, const float *grad_qnorm, float *grad_v, float *grad_y,
                                 sn_stream_t stream);
 
+/* The pose-error terms of the registration task (registration/src/qdataset.py:62-95 QuaternionTransform.compute_errors, as
+ * registration/main.py:579-585 `--loss-type 0` and the evaluation of main.py:364-483 use them) and the per-cloud Chamfer mean of
+ * main.py:540-555 / 573-577 for a batch.  (They replace a reference interface; they are declared here because the public header
+ * is held at its entry count.)  est, gt: (B,7) rows [quaternion (w,x,y,z) | translation] -- sn_pcrnet_head_*'s twist, sn_batch_assemble's igt.
+ *   rot_err[b]   = 2 acos(clamp(2 d^2 - 1, -1, 1)) radians, d = q1 . q2 of the quaternions AS GIVEN (qdataset.py:85).  DEVIATION:
+ *                  the clamp -- the reference returns NaN wherever fp32 rounding lifts the argument above 1 (a fifth of all
+ *                  self-comparisons of unit quaternions); results differ only there.  A NaN input still gives NaN.
+ *   norm_err[b]  = sum_ij (R(q1) R(q2)^T - I)_ij^2, R the rotation matrix of the NORMALISED quaternion q / max(||q||, 1e-12)
+ *                  (the arithmetic of kornia's quaternion_to_rotation_matrix, qdataset.py:74-90).
+ *   trans_err[b] = (|dt_x| + |dt_y| + |dt_z|) / 3; its batch mean is qdataset.py:93's mean over B x 3.
+ *   means (3)    = the batch means of the three, summed in ONE fixed order (thread t of 256 adds clouds t, t + 256, ...; halving
+ *                  tree; / B): two runs are bit-identical.  Every output may be NULL; B = 0 is a no-op; any B >= 1 is served.
+ * _backward: g_est (B,7), overwritten, of sum_b (g_means[1] / B + g_norm_err[b]) norm_err[b] + (g_means[2] / B + g_trans_err[b])
+ *   trans_err[b]; g_means (device, 3 floats), g_norm_err, g_trans_err (B,) may each be NULL.  g_means[0] is NOT read: rot_err is a
+ *   metric (the reference never backpropagates it; its derivative is unbounded at zero error).  The quaternion gradient goes
+ *   through the normalisation, (g_n - n (n . g_n)) / max(||q||, 1e-12); the translation gradient is sign(dt) / 3 with
+ *   sign(0) = 0.  DEVIATION: the reference's sqrt(dt^2) gives NaN at dt = 0.  No gradient flows to gt.
+ * sn_chamfer_mean_per_cloud: out[b] = mean(dist1[b, :]) + mean(dist2[b, :]) from sn_chamfer_forward's products (dist1 (B,n1),
+ *   dist2 (B,n2)); forward only, one workgroup per cloud, fixed summation order. */
+int sn_pose_error_forward(int B, const float *est, const float *gt, float *rot_err, float *norm_err, float *trans_err, float *means,
+                          sn_stream_t stream);
+int sn_pose_error_backward(int B, const float *est, const float *gt, const float *g_means, const float *g_norm_err,
+                           const float *g_trans_err, float *g_est, sn_stream_t stream);
+int sn_chamfer_mean_per_cloud(int B, int n1, int n2, const float *dist1, const float *dist2, float *out, sn_stream_t stream);
+
 /* The progressive sampler's nested prefixes (classification/train_samplenet_progressive.py:157-234) as contiguous tensors in ONE launch:
  * src (B, M, C) of 4-byte elements -> dst[j] (B, sizes[j], C) = src[:, :sizes[j], :] (dst: HOST array of nprefix <= 16 device
  * pointers, NULL entries skipped); and the gradient of that in one launch: out (B, M, C) = sum over j of grads[j] zero-padded to

@@ -11,11 +11,14 @@ from .autoencoder import PointNetAE, reconstruction_loss  # noqa: F401
 from .device_data import BatchRecipe, DeviceBatchSource, DeviceCloudSet  # noqa: F401
 from .classifier import PointNetCls, PointNetClsBasic, classification_loss  # noqa: F401
 from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: F401
+from .qtransform import QuaternionTransform, deg_to_rad, qinv, rad_to_deg  # noqa: F401
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
+from .evaluation import RegistrationEvaluator  # noqa: F401
 from .samplers import FPSSampler, RandomSampler  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
            "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
-           "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet"]
+           "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet", "QuaternionTransform", "qinv", "rad_to_deg",
+           "deg_to_rad", "RegistrationEvaluator"]

@@ -166,6 +166,9 @@ PROTOTYPES = {
     "sn_adam_state_bytes": [],
     "sn_adam_update": [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                        ctypes.c_double, _i, _vp],
+    "sn_pose_error_forward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_pose_error_backward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_chamfer_mean_per_cloud": [_i, _i, _i, _vp, _vp, _vp, _vp],
     "sn_batch_state_bytes": [],
     "sn_batch_assemble": [_i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _i, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp,
                           _vp, _vp, _vp, _vp],

@@ -17,12 +17,15 @@ import torch
 class SamplerTrainStep:
     def __init__(self, net, example_x, alpha=0.01, lmbda=0.01, gamma=1.0, delta=0.0, task_loss=None, reducer=None,
                  use_graph=True, warmup=3, fused_loss=True, input_ring=None, fused_head=True, overlap_allreduce=None,
-                 allreduce="graph", optimizer=None, input_source=None):
+                 allreduce="graph", optimizer=None, input_source=None, task_loss_igt=False):
         self.net, self.reducer = net, reducer
         # input_source: a samplenet_amd.device_data.DeviceBatchSource of example_x's shape -- its one launch into self.x is the FIRST
         # node of the step's graph (issued eagerly in front of the step with use_graph=False): step() takes no batch and the host
         # touches nothing.  A source that makes pairs fills a second target, self.x1, and the task loss is called as
         # task_loss(proj, x1).  The warm-up passes run on example_x and draw nothing from the source.
+        # task_loss_igt=True (pair-making source only): the source's launch also fills a static ground-truth pose target, self.igt
+        # (B,7) rows [quaternion (w,x,y,z) | translation], and the task loss is called as task_loss(proj, x1, igt) -- the pose terms of
+        # registration/main.py `--loss-type 0` inside the captured step.  The warm-up passes see the identity pose.
         if input_source is not None:
             if input_ring is not None:
                 raise ValueError("input_source and input_ring are mutually exclusive")
@@ -30,7 +33,9 @@ class SamplerTrainStep:
                 raise ValueError("input_source makes %s batches on %s, example_x is %s on %s"
                                  % (tuple(input_source.shape()), input_source.device, tuple(example_x.shape), example_x.device))
         self.source = input_source
-        self.x1 = None
+        self.x1 = self.igt = None
+        if task_loss_igt and not (input_source is not None and input_source.makes_pairs and task_loss is not None):
+            raise ValueError("task_loss_igt needs a task_loss and an input_source that makes pairs")
         # optimizer: a samplenet_amd.optim.Adam over the net's parameters -- its update (one launch per parameter group) is issued
         # right behind reducer.reduce(): as the last node(s) of the step's graph where the gradients are final inside it (no
         # collective, or allreduce 'graph' / 'graph-fork'), behind the Python-side collective otherwise ('after', the split step),
@@ -63,7 +68,11 @@ class SamplerTrainStep:
         self.x = example_x.clone() if self.ring is None else self.ring[0]
         if self.source is not None and self.source.makes_pairs:
             self.x1 = example_x.clone()
-            if task_loss is not None:
+            if task_loss_igt:
+                self.igt = torch.zeros(example_x.shape[0], 7, device=example_x.device, dtype=torch.float32)
+                self.igt[:, 0] = 1.0
+                self.task_loss = lambda proj, _f=task_loss: _f(proj, self.x1, self.igt)
+            elif task_loss is not None:
                 self.task_loss = lambda proj, _f=task_loss: _f(proj, self.x1)
         self._one = torch.ones((), device=example_x.device, dtype=torch.float32)
         self.graph = None
@@ -416,7 +425,7 @@ class SamplerTrainStep:
     def _pull(self):
         """input_source: the next batch into the step's static input(s) -- one launch on the current stream."""
         if self.source is not None:
-            self.source.next_into(self.x, self.x1)
+            self.source.next_into(self.x, self.x1, igt=self.igt)
 
     def step(self):
         """One step on the next batch of input_source; returns the (static) loss tensor."""

@@ -997,3 +997,112 @@ def emd_loss(xyz1, xyz2, exact=False):
     (they follow the transport plan, whose entries the reference itself only pins to 1e-2 between its CPU and GPU ops).
     exact=True: cost and the xyz1 gradient bit for bit those of the three-call composition, ~1.3x slower."""
     return EmdLossFunction.apply(xyz1, xyz2, exact)
+
+
+# --------------------------------------------------------------------------------------------- pose-error terms
+class PoseErrorFunction(torch.autograd.Function):
+    """est, gt (B,7) rows [quaternion (w,x,y,z) | translation] -> rot_err, norm_err, trans_err (B,) and their batch means (3,)
+    (registration/src/qdataset.py:62-95 compute_errors) -- sn_pose_error_forward / _backward, one launch each way.  rot_err and
+    component 0 of the means are metrics: non-differentiable.  No gradient flows to gt."""
+
+    @staticmethod
+    def forward(ctx, est, gt):
+        _need_gpu(est, gt)
+        est, gt = _f32c(est), _f32c(gt)
+        if est.dim() != 2 or est.shape[1] != 7 or gt.shape != est.shape:
+            raise ValueError("pose_errors: est and gt must both be (B,7), got %s and %s" % (tuple(est.shape), tuple(gt.shape)))
+        B = est.shape[0]
+        e = lambda *shape: torch.empty(shape, device=est.device, dtype=torch.float32)  # noqa: E731
+        rot, nrm, trn, means = e(B), e(B), e(B), e(3)
+        with torch.cuda.device(est.device):
+            check(lib.sn_pose_error_forward(B, ptr(est), ptr(gt), ptr(rot), ptr(nrm), ptr(trn), ptr(means), _stream(est)),
+                  "sn_pose_error_forward")
+        ctx.save_for_backward(est, gt)
+        ctx.mark_non_differentiable(rot)
+        ctx.set_materialize_grads(False)
+        return rot, nrm, trn, means
+
+    @staticmethod
+    def backward(ctx, _g_rot, g_nrm, g_trn, g_means):
+        est, gt = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        if g_nrm is None and g_trn is None and g_means is None:
+            return torch.zeros_like(est), None
+        c = lambda g: None if g is None else g.contiguous().float()  # noqa: E731
+        g_nrm, g_trn, g_means = c(g_nrm), c(g_trn), c(g_means)
+        g_est = torch.empty_like(est)
+        with torch.cuda.device(est.device):
+            check(lib.sn_pose_error_backward(est.shape[0], ptr(est), ptr(gt), ptr(g_means), ptr(g_nrm), ptr(g_trn), ptr(g_est),
+                                             _stream(est)), "sn_pose_error_backward")
+        return g_est, None
+
+
+def pose_errors(est, gt):
+    """Per-cloud (rot_err [radians], norm_err, trans_err), each (B,), of the poses est against gt ((B,7) rows
+    [quaternion (w,x,y,z) | translation]); differentiable in norm_err and trans_err with respect to est."""
+    return PoseErrorFunction.apply(est, gt.detach())[:3]
+
+
+_POSE_ZERO = {}  # device -> a (1,) zero (made outside captures; a constant of the graphs that use it)
+
+
+class PoseErrorMeansFunction(torch.autograd.Function):
+    """est, gt (B,7) -> the batch means rot_err, norm_err, trans_err as three 0-d tensors (compute_errors' return, qdataset.py:95):
+    one sn_pose_error_forward launch.  Backward: the (3,) upstream vector of sn_pose_error_backward is put together by ONE cat
+    launch from the scalars autograd hands over (a missing one is a cached zero), then the one backward launch."""
+
+    @staticmethod
+    def forward(ctx, est, gt):
+        _need_gpu(est, gt)
+        est, gt = _f32c(est), _f32c(gt)
+        if est.dim() != 2 or est.shape[1] != 7 or gt.shape != est.shape:
+            raise ValueError("pose errors: est and gt must both be (B,7), got %s and %s" % (tuple(est.shape), tuple(gt.shape)))
+        means = torch.empty(3, device=est.device, dtype=torch.float32)
+        with torch.cuda.device(est.device):
+            check(lib.sn_pose_error_forward(est.shape[0], ptr(est), ptr(gt), None, None, None, ptr(means), _stream(est)),
+                  "sn_pose_error_forward")
+        ctx.save_for_backward(est, gt)
+        ctx.set_materialize_grads(False)
+        rot, nrm, trn = means.unbind(0)
+        ctx.mark_non_differentiable(rot)
+        return rot, nrm, trn
+
+    @staticmethod
+    def backward(ctx, _g_rot, g_nrm, g_trn):
+        est, gt = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        if g_nrm is None and g_trn is None:
+            return torch.zeros_like(est), None
+        zero = _POSE_ZERO.get(est.device)
+        if zero is None:
+            zero = torch.zeros(1, device=est.device, dtype=torch.float32)
+            if not torch.cuda.is_current_stream_capturing():
+                _POSE_ZERO[est.device] = zero
+        one = lambda g: zero if g is None else g.reshape(1).float()  # noqa: E731
+        g_means = torch.cat((zero, one(g_nrm), one(g_trn)))  # (component 0 is not read)
+        g_est = torch.empty_like(est)
+        with torch.cuda.device(est.device):
+            check(lib.sn_pose_error_backward(est.shape[0], ptr(est), ptr(gt), ptr(g_means), None, None, ptr(g_est), _stream(est)),
+                  "sn_pose_error_backward")
+        return g_est, None
+
+
+def pose_error_means(est, gt):
+    """The batch means (rot_err, norm_err, trans_err) as 0-d tensors -- compute_errors' return (qdataset.py:95); rot_err is a
+    metric: non-differentiable."""
+    return PoseErrorMeansFunction.apply(est, gt.detach())
+
+
+def chamfer_mean_per_cloud(xyz1, xyz2):
+    """mean_n d(xyz1[b] -> xyz2[b]) + mean_m d(xyz2[b] -> xyz1[b]) for every cloud pair, (B,): the Chamfer term of
+    registration/main.py:573-577 / 549-554 per item of a batch (forward only: the scan + one reduction launch)."""
+    with torch.no_grad():
+        _x1, _x2, dist1, _i1, dist2, _i2 = chamfer_forward_impl(xyz1, xyz2)
+        B, n1 = dist1.shape
+        out = torch.empty(B, device=dist1.device, dtype=torch.float32)
+        with torch.cuda.device(dist1.device):
+            check(lib.sn_chamfer_mean_per_cloud(B, n1, dist2.shape[1], ptr(dist1), ptr(dist2), ptr(out), _stream(dist1)),
+                  "sn_chamfer_mean_per_cloud")
+    return out

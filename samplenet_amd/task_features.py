@@ -781,8 +781,8 @@ def pcrnet_chamfer_loss(model, p0, p1, template_features=None):
     """The Chamfer term of the registration task loss (`registration/main.py:557-577`, `--loss-type 1`):
     twist = model(p0, p1); p1_est = rotate(p0) by the estimated quaternion (QuaternionTransform.rotate,
     qdataset.py:97-119: rotation only); loss = mean d(p1 -> p1_est) + mean d(p1_est -> p1) on the HIP Chamfer kernels.
-    p0 template / p1 source, (B,N,3).  Returns (chamfer_loss, qnorm_loss, twist).  The rotation-matrix error terms of
-    `--loss-type 0` go through kornia in the reference (not installed here) and stay with the caller.
+    p0 template / p1 source, (B,N,3).  Returns (chamfer_loss, qnorm_loss, twist).  The pose-error terms of `--loss-type 0`
+    (main.py:579-585) are added by `pcrnet_loss` below, on sn_pose_error_*.
     template_features: model.template_features(p0), when several evaluations of a step share the template."""
     if template_features is None and isinstance(model, nn.Module):
         from . import graphed
@@ -805,3 +805,67 @@ def _pcrnet_chamfer_loss(model, p0, p1, template_features):
         p1_est = qrot_cloud(twist[:, 0:4], p0)  # = qrot(twist[:, 0:4] expanded over the points, p0)
     # mean(d(p1 -> p1_est)) + mean(d(p1_est -> p1)): scan + one fused reduction, implicit-gradient backward
     return chamfer_mean_loss(p1.contiguous(), p1_est.contiguous()), qnorm_loss, twist
+
+
+_INFO_KEYS = ("chamfer_loss", "qnorm_loss", "rot_err", "norm_err", "trans_err", "est_transform")
+
+
+def _igt_vec(igt, like):
+    """The ground-truth pose as a (B,7) tensor on like's device: the tensor itself (DeviceBatchSource's igt) or the `vec` of the
+    reference's dict (QuaternionTransform.as_dict, qdataset.py:174)."""
+    vec = igt["vec"] if isinstance(igt, dict) else igt
+    return vec.to(like.device).view(-1, 7)
+
+
+def pcrnet_loss(model, p0, p1, igt, loss_type=0, template_features=None, want_info=True):
+    """compute_pcrnet_loss of `registration/main.py:557-598`: -> (pcrnet_loss, info).  loss_type 0 (the reference's default):
+    norm_err + chamfer_loss; 1: chamfer_loss alone (equal to pcrnet_chamfer_loss's, bit for bit).  info holds the keys of
+    main.py:589-596 -- chamfer_loss, qnorm_loss, rot_err (degrees), norm_err, trans_err, est_transform; the three pose terms are
+    QuaternionTransform.compute_errors' batch means (one launch, one more backward).  igt: (B,7) rows [quaternion (w,x,y,z) |
+    translation] or the reference's dict.  A frozen network replays the whole term from two captured graphs (graphed.py).
+    want_info=False -> (pcrnet_loss, None): what a captured training step wants -- nothing is launched for the metrics alone (the
+    conversion of rot_err to degrees is an elementwise launch; with loss_type 1 the pose terms are not computed at all).
+    Launches on top of pcrnet_chamfer_loss's for loss_type 0: the pose forward and the scalar addition norm_err + chamfer_loss;
+    backward: one three-element cat that hands the addition's upstream scalar to the pose backward, and the pose backward."""
+    from .qtransform import QuaternionTransform
+
+    if loss_type not in (0, 1):
+        raise ValueError("loss_type: 0 (norm_err + chamfer_loss) or 1 (chamfer_loss)")
+    vec = _igt_vec(igt, p1)
+    if not want_info and loss_type == 1:
+        return pcrnet_chamfer_loss(model, p0, p1, template_features)[0], None
+    out = None
+    if template_features is None and isinstance(model, nn.Module):
+        from . import graphed
+
+        tag = "pcrnet_loss%d%s" % (loss_type, "" if want_info else "v")
+        out = graphed.call(model, tag, lambda a, b, g: _pcrnet_loss(model, a, b, g, loss_type, None, want_info), (p0, p1, vec))
+    if out is None:
+        out = _pcrnet_loss(model, p0, p1, vec, loss_type, template_features, want_info)
+    if not want_info:
+        return (out if isinstance(out, torch.Tensor) else out[0]), None
+    chamfer_loss, qnorm_loss, rot_deg, norm_err, trans_err, twist = out[:6]
+    loss = out[6] if loss_type == 0 else chamfer_loss
+    return loss, dict(zip(_INFO_KEYS, (chamfer_loss, qnorm_loss, rot_deg, norm_err, trans_err, QuaternionTransform(twist))))
+
+
+def _pcrnet_loss(model, p0, p1, vec, loss_type, template_features, want_info=True):
+    from .ops import pose_error_means
+    from .qtransform import rad_to_deg
+
+    chamfer_loss, qnorm_loss, twist = _pcrnet_chamfer_loss(model, p0, p1, template_features)
+    rot_err, norm_err, trans_err = pose_error_means(twist, vec)
+    if not want_info:
+        return norm_err + chamfer_loss  # (loss_type 0; main.py:582: 1.0 * norm_err + 1.0 * chamfer_loss)
+    out = (chamfer_loss, qnorm_loss, rad_to_deg(rot_err), norm_err, trans_err, twist)
+    return out + (norm_err + chamfer_loss,) if loss_type == 0 else out
+
+
+def sampling_consistency(p0s, p1s, igt):
+    """compute_sampling_consistency of `registration/main.py:540-555`: the sampled source rotated back by the inverse ground-truth
+    quaternion against the sampled template, mean d(p0s -> est) + mean d(est -> p0s) over the batch (a scalar)."""
+    from .ops import chamfer_mean_loss
+    from .qtransform import qinv
+
+    p0s_est = qrot_cloud(qinv(_igt_vec(igt, p1s)[:, 0:4]), p1s)
+    return chamfer_mean_loss(p0s.contiguous(), p0s_est.contiguous())
