@@ -108,10 +108,9 @@ __device__ __forceinline__ void store_sc1_b128(float *p, f32x4v v)
 // caller then poisons its outputs with NaN, and the error word stays set for the loss tail / the host (sn_fc_chain_error).
 // Poll bound: sync[13] when non-zero (tests), else 2^22 polls (seconds).
 constexpr int kFcChainPolls = 1 << 22;
-// the words of a chain launch's `sync` state sit 128 bytes apart (word i at sync[i * kFcSyncStride]): epoch, the per-seam
-// arrival counters, the poll bound and the error word each own a cache line -- 8..16 workgroups add to and poll different
-// counters at the same time, and on ONE line every poll queues behind the others' atomics
-constexpr int kFcSyncStride = SN_FC_SYNC_STRIDE;
+// the words of a chain launch's `sync` state sit 128 bytes apart (word i at sync[i * kFcSyncStride], sn_common.h): epoch, the
+// per-seam arrival counters, the poll bound and the error word each own a cache line -- 8..16 workgroups add to and poll
+// different counters at the same time, and on ONE line every poll queues behind the others' atomics
 __device__ __forceinline__ bool fc_chain_seam(unsigned *sync, int ctr, unsigned epoch, int nwg, unsigned errcode, int limit)
 {
     __hip_atomic_fetch_add(sync + ctr * kFcSyncStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -20,13 +20,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef SN_BF16X3
 #define SN_BF16X3 1  // conv-stack GEMMs: fp32 products as split-bf16 products on the bf16 matrix cores (gemm_tile_bx3)
 #endif
-#ifndef SN_FWD_KT128
-#define SN_FWD_KT128 0  // 128 input channels: chunk-by-chunk prefetch (fetching the whole K = 128 up front measured slower)
-#endif
-#ifndef SN_FWD_TW
-#define SN_FWD_TW Tile<64, 128, 2, 4>  // conv layers with 128 output channels: one 512-thread workgroup per 64 rows (Tile<64, 128, 2, 2>,
-                                       // 32 x 64 per wave, half the LDS fragment traffic: 17.5 vs 15.8 us on the 128 -> 128 layer)
-#endif
 constexpr int BK = 64;   // K chunk (one chunk covers the 64-channel layers: a single exposed global-load latency)
 constexpr int LPAD = 4;  // LDS row padding (floats): keeps rows 16-B aligned for the float4 staging stores
 
@@ -64,10 +57,7 @@ enum { ACT_NONE = 0, ACT_BN_RELU = 1, ACT_BN_RELU_FX = 2 };
 // Same-address device-scope atomics serialise at the memory side (~20 ns per 128-byte line operation, measured: 512
 // workgroups adding into one set of sums cost ~10 us per layer): the workgroups spread over kFxSlots copies
 // (swept 4 / 8 / 16 / 32: 243.5 / 240.3 / 239.2 / 255.5 us per step).
-#ifndef SN_FX_SLOTS
-#define SN_FX_SLOTS 16
-#endif
-constexpr int kFxSlots = SN_FX_SLOTS;
+constexpr int kFxSlots = 16;
 constexpr int kFxRow = 128;                           // channels per row (a layer of 129 .. 256 channels: TWO blocks back to back,
                                                       //  channel c in block c >> 7 -- sn_conv_stack_forward_bn's wide layout)
 constexpr int kFxHi = kFxSlots * 2 * kFxRow;          // lo rows [slot][stat][128], then ONE pair of hi rows [stat][128]
@@ -535,23 +525,13 @@ constexpr int LDX = BKX + 8;  // LDS row pitch in bf16: 80 bytes -- 16 consecuti
 
 // Staging map of the K chunks: item f (4 consecutive k of one row: 8 bytes per plane) -> row.  The 16 lanes of a ds_write_b64 lane
 // group hold two rows; rows x and x + 1 are 80 bytes apart (banks 20-35 wrap onto 0-3: a 2-way conflict on every store of the three
-// planes -- the 20-29 % conflict share of the forward kernels' LDS cycles in profiles/r06/lds_map.txt).  SN_BX3_ROWMAP=1 pairs rows x
-// and x + 4 instead (320 bytes apart: disjoint halves of the stores' 32 banks; a bijection inside every block of 8 rows) -- built and
+// planes -- the 20-29 % conflict share of the forward kernels' LDS cycles in profiles/r06/lds_map.txt).  A map pairing rows x and
+// x + 4 instead (320 bytes apart: disjoint halves of the stores' 32 banks; a bijection inside every block of 8 rows) was built and
 // measured in round 6: bit-identical, and NOT faster (B = 2048: 548.7 / 324.6 / 215.2 / 185.4 us against 551.0 / 330.0 / 214.1 / 183.1;
-// B = 32 equal): LDS stores are paced by the register transfer, not by the array (MI355X_MICROARCH.md, LDS).  Left off.
-#ifndef SN_BX3_ROWMAP
-#define SN_BX3_ROWMAP 0
-#endif
-__device__ __forceinline__ constexpr int bx3_row(int f)
-{
-    return SN_BX3_ROWMAP ? (((f >> 6) << 3) + ((f >> 4) & 3) + (((f >> 3) & 1) << 2)) : f / (BKX / 4);
-}
-static_assert(BKX == 32, "bx3_row: 8 items per row");
+// B = 32 equal): LDS stores are paced by the register transfer, not by the array (MI355X_MICROARCH.md, LDS).  Removed.
+__device__ __forceinline__ constexpr int bx3_row(int f) { return f / (BKX / 4); }
 // the same for 16-byte items (pre-split weight planes: 4 items per row, ds_write_b128 in lane groups of 8 = two rows)
-__device__ __forceinline__ constexpr int bx3_row8(int f)
-{
-    return SN_BX3_ROWMAP ? (((f >> 5) << 3) + ((f >> 3) & 3) + (((f >> 2) & 1) << 2)) : f / (BKX / 8);
-}
+__device__ __forceinline__ constexpr int bx3_row8(int f) { return f / (BKX / 8); }
 
 __device__ __forceinline__ void split3(float a, __bf16 &h1, __bf16 &h2, __bf16 &h3)
 {

@@ -356,9 +356,6 @@ __device__ __forceinline__ void fx_local_add(long long &lo, long long *layer, in
     }
 }
 
-#ifndef SN_FWDP_ABL
-#define SN_FWDP_ABL 0  // (timing experiments only: 1 no MFMAs, 2 no staging of the next tile, 3 no stores of Z, 6 two accumulator chains)
-#endif
 template <class T, int KT, bool IN3A, int WPE>
 __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) linear_fwd_persist_kernel(FwdArgs g, int ntiles,
                                                                                                                          int tpw)
@@ -511,37 +508,21 @@ __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu
     // overlaps the MFMAs of the others.
     const auto process = [&](int tile, float4 (&nxt)[NCH][A4]) {
         const int buf = (tile - tile0) & 1;
-        if (tile + 1 < tile1 && SN_FWDP_ABL != 2) stage(nxt, buf ^ 1);
+        if (tile + 1 < tile1) stage(nxt, buf ^ 1);
         if (tile + 3 < tile1) fetch_tile(nxt, tile + 3);
         const int row0 = tile * T::BM;
         f32x16 acc;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
         const __bf16 *At = Abuf + buf * ABUF;
-#if SN_FWDP_ABL == 6
-        f32x16 acc2;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
-#endif
-#pragma unroll
-        for (int ks = 0; ks < (SN_FWDP_ABL == 1 ? 0 : KS); ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {
             const __bf16 *Ap = At + (ks / (BKX / 16)) * ACH;
             const int kk = ks % (BKX / 16);
             bf16x8 a[3];
 #pragma unroll
             for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8 *>(Ap + (p * T::BM + wr * 32 + l31) * LDX + kk * 16 + 8 * h);
             // smallest products first (the order of bx3_chunk_g)
-#if SN_FWDP_ABL == 6
-            if (ks & 1) {
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], breg[ks][2], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], breg[ks][0], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], breg[ks][1], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], breg[ks][1], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], breg[ks][0], acc2, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], breg[ks][0], acc2, 0, 0, 0);
-                continue;
-            }
-#endif
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], breg[ks][2], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], breg[ks][0], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], breg[ks][1], acc, 0, 0, 0);
@@ -549,10 +530,6 @@ __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], breg[ks][0], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], breg[ks][0], acc, 0, 0, 0);
         }
-#if SN_FWDP_ABL == 6
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] += acc2[e];
-#endif
         // ---- epilogue: bias, column sums, pool candidates, 16-byte stores through the wave's transpose scratch
         float s0 = 0.f, s1 = 0.f, pmax = -INFINITY, pmin = INFINITY;
         int imax = 0, imin = 0;
@@ -570,7 +547,7 @@ __global__ void __launch_bounds__(T::THREADS) __attribute__((amdgpu_waves_per_eu
                 if (v > pmax) pmax = v, imax = row;
                 if (v < pmin) pmin = v, imin = row;
             }
-            if (g.z && SN_FWDP_ABL != 3) {
+            if (g.z) {
                 const sn_rsrc zt = make_rsrc(g.z + (size_t)row0 * Co, (unsigned)(T::BM * Co) * 4);  // (this tile's rows; SN_ST_Z)
                 const unsigned zvo = (unsigned)((lane >> 3) * Co + (lane & 7) * 4) * 4;
                 const unsigned zso = (unsigned)((wr * 32 + 16 * hf) * Co + wc * 32) * 4;
@@ -1805,9 +1782,6 @@ extern "C" int sn_conv_stack_set_persist_min_tiles(int tiles)
     g_persist_min_tiles = tiles;
     return old;
 }
-#ifndef SN_FWD_HT
-#define SN_FWD_HT 1
-#endif
 template <class TT, int KT, bool IN3A>
 static int launch_fwd_persist(const FwdArgs &g, int ntiles, int tpw, int nwg, hipStream_t st)
 {
@@ -1907,18 +1881,16 @@ extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *ch
                 const int tpw = (ntiles + nmax - 1) / nmax, nwg = (ntiles + tpw - 1) / tpw;
                 if (l == 1) g.x3 = x, g.w3 = W[0], g.b3 = bias ? bias[0] : nullptr;
                 int rc = 0;
-                // 128 output channels: TWO 256-thread workgroups per CU on 32-row tiles (SN_FWD_HT) instead of one 512-thread
+                // 128 output channels: TWO 256-thread workgroups per CU on 32-row tiles instead of one 512-thread
                 // workgroup on 64-row tiles -- the eight waves of one tile stage, multiply and store in lockstep (one barrier per
                 // tile): a SIMD's two waves are always in the same phase; two independent workgroups drift apart and the
                 // dependent MFMA chain of one overlaps the staging / epilogue of the other
-                const bool ht = SN_FWD_HT && Co == 128 && l != 1;
+                const bool ht = Co == 128 && l != 1;
                 const int nmax_h = device_cus() * 2, tpw_h = 2 * ((ntiles + nmax_h - 1) / nmax_h), nwg_h = (2 * ntiles + tpw_h - 1) / tpw_h;
                 using THT = Tile<32, 128, 1, 4>;
                 if (l == 1) rc = launch_fwd_persist<T, 64, true>(g, ntiles, tpw, nwg, st);
                 else if (ht && Ci == 128) rc = launch_fwd_persist<THT, 128, false>(g, 2 * ntiles, tpw_h, nwg_h, st);
                 else if (ht) rc = launch_fwd_persist<THT, 64, false>(g, 2 * ntiles, tpw_h, nwg_h, st);
-                else if (Co == 128 && Ci == 128) rc = launch_fwd_persist<SN_FWD_TW, 128, false>(g, ntiles, tpw, nwg, st);
-                else if (Co == 128) rc = launch_fwd_persist<SN_FWD_TW, 64, false>(g, ntiles, tpw, nwg, st);
                 else rc = launch_fwd_persist<T, 64, false>(g, ntiles, tpw, nwg, st);
                 if (rc) return rc;
                 continue;
@@ -1937,7 +1909,7 @@ extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *ch
             // 128 output channels: one 512-thread workgroup per 64 rows computes all of them -- the input tile is fetched
             // once instead of once per 64-column block, and half as many workgroups run the statistics prologue
             // (256 output channels: two such column blocks)
-            using TW = SN_FWD_TW;
+            using TW = TileWide;
             const dim3 grid(R / TW::BM, Co / TW::BN);
             const size_t lds = shaped_lds(lds_bytes<TW>() + (size_t)2 * Ci * sizeof(float), grid);
 #define SN_FWD_FX(TT, KT_)                                                                                                \
@@ -1949,14 +1921,14 @@ extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *ch
                 SN_REQUIRE(pl, "a 256-channel input needs the pre-split weight planes");
                 hipLaunchKernelGGL((linear_fwd_kernel<TW, true, ACT_BN_RELU_FX, 256, SN_BF16X3 != 0>), grid, dim3(TW::THREADS), lds, st, g);
             } else if (Ci == 128 && pl) SN_FWD_FX(TW, 128);
-            else if (Ci == 128) SN_FWD_FX(TW, SN_FWD_KT128);
+            else if (Ci == 128) SN_FWD_FX(TW, 0);  // chunk-by-chunk prefetch (fetching the whole K = 128 up front measured slower)
             else SN_FWD_FX(TW, 64);
             continue;
         }
         const dim3 grid(R / T::BM, Co / T::BN);
         const size_t lds = shaped_lds(lds_bytes<T>() + (size_t)2 * Ci * sizeof(float), grid);
         if (Ci == 128 && pl) SN_FWD_FX(T, 128);
-        else if (Ci == 128) SN_FWD_FX(T, SN_FWD_KT128);
+        else if (Ci == 128) SN_FWD_FX(T, 0);  // (chunk-by-chunk, as above)
         else SN_FWD_FX(T, 64);
 #undef SN_FWD_FX
     }

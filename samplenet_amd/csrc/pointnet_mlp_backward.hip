@@ -762,35 +762,6 @@ __device__ __forceinline__ bf16x8 lds_tr8_2(const __bf16 *plo, const __bf16 *phi
     return __builtin_bit_cast(bf16x8, v);
 }
 
-#ifndef SN_CBX_PW
-#define SN_CBX_PW 3  // bit 0: the plain layers, bit 1: the layer above the xyz layer (the activation tile rebuilt from the coordinates)
-#endif
-#ifndef SN_CBX_PD
-#define SN_CBX_PD 1  // (2: tile t + 2 of the activation requested while t + 1 waits -- measured SLOWER, 909 -> 1050 us at B = 2048)
-#endif
-#ifndef SN_CBX_DG2
-#define SN_CBX_DG2 0  // (1: two accumulator chains in the data gradient -- measured equal: 939 vs 945 us at B = 2048, 21.3 vs 21.5 at B = 32)
-#endif
-#ifndef SN_CBX_ABL
-#define SN_CBX_ABL 0  // (timing experiments only: 1 no data-gradient MFMAs, 2 no weight-gradient MFMAs / fragment reads, 3 no dYprev stores,
-#endif                //  4 no staging, 5 no data-gradient epilogue, 6 no Zprev re-loads for the epilogue -- results are then garbage)
-#ifndef SN_CBX_SWZ
-#define SN_CBX_SWZ 1  // conflict-free LDS layout of the 128 x 128 kernel's tile planes (CbxShape::SWZ); 0: the round-5 layout (A/B)
-#endif
-#ifndef SN_CBX_SKEW
-#define SN_CBX_SKEW 1  // the 128 x 128 kernel's two wave groups half a tile apart (see kSkew in conv_bwd_bx3_kernel); 0: in lockstep (A/B)
-#endif
-#ifndef SN_CBX_LATE_ST
-#define SN_CBX_LATE_ST 0  // (1: the previous tile's dYprev stores behind the first k-step's MFMAs, see store_prev -- measured: 128 x 128 772 -> 765 us,
-                          //  64 -> 128 616 -> 648, 64 x 64 376 -> 395 at B = 2048: the acknowledgements are not what the waves wait for)
-#endif
-#ifndef SN_CBX_SKEW_DG2
-#define SN_CBX_SKEW_DG2 0  // (1: two accumulator chains in the skewed kernel's data gradient -- measured equal, 795 vs 784-794 us: one chain
-                          //  issues at the pipe's rate, tools/micro/mfma_bf16_chain.hip; 0 keeps the round-5 kernel's bits)
-#endif
-#ifndef SN_CBX_CONTIG
-#define SN_CBX_CONTIG 0  // (1: a contiguous range of tiles per workgroup -- measured equal to -6 %)
-#endif
 template <int CI, int CO>
 struct CbxShape {
     static constexpr int TR = CO == 128 ? 32 : 64;                  // two tile buffers of three planes must fit the LDS
@@ -799,7 +770,7 @@ struct CbxShape {
     // land on four disjoint 16-bank windows (272-byte rows: 4-way conflicts, half of the kernel's LDS cycles) -- and, in the dZ planes,
     // the 16-byte slots of a row XOR-ed with (row / 4) % 4, which keeps the data-gradient waves' row-wise 16-byte reads (lane groups
     // {0-3, 12-15, 20-27}, ...) conflict-free at that pitch; the XOR stays inside a 64-byte window, so the transposing reads keep theirs
-    static constexpr bool SWZ = SN_CBX_SWZ != 0 && CO == 128;
+    static constexpr bool SWZ = CO == 128;
     static constexpr int LDZ = SWZ ? 160 : CO + 8, LDP = SWZ ? (CI == 128 ? 160 : 96) : CI + 8;  // (96: 192-byte rows, windows 0, 48, 32, 16)
     static constexpr int ZPL = TR * LDZ, PPL = TR * LDP;            // one plane
     static constexpr int BUF = 3 * (ZPL + PPL);                     // bf16 elements per tile buffer
@@ -811,20 +782,17 @@ struct CbxShape {
     static_assert(LDS_BYTES_IN3 <= 160 * 1024, "tile buffers exceed the LDS");
 };
 
-// RZ1: rp[q] holds the xyz coordinates of the row; w3 -> the xyz layer's (w0, w1, w2, bias) of this thread's four channels, in LDS
-template <int CO, int CI, int TR, int ZMODE, bool FULLR, int NZ4, int NP4, bool RZ1 = false, bool SKIP_PS = false>
+// the dZ tile of the producer waves: BatchNorm backward (or the pool's scatter), split, into the three planes at Zb
+template <int CO, int CI, int TR, int ZMODE, bool FULLR, int NZ4>
 __device__ __forceinline__ void cbx_stage(const ConvBwdArgs &g, int tile, int n0, int tid, __bf16 *__restrict__ Zb,
-                                          __bf16 *__restrict__ Pb, const float4 (&rz)[NZ4], const float4 (&rdy)[NZ4],
-                                          const float4 (&rp)[NP4], const int4 &rag, const float4 &rgs, const float4 &k1,
-                                          const float4 &k2, const float4 &k3, const float4 &sc4, const float4 &sh4,
-                                          const float4 *w3 = nullptr)
+                                          const float4 (&rz)[NZ4], const float4 (&rdy)[NZ4], const int4 &rag, const float4 &rgs,
+                                          const float4 &k1, const float4 &k2, const float4 &k3)
 {
-    constexpr int ZSTEP = 256 / (CO / 4), PSTEP = 256 / (CI / 4);
-    constexpr int LDZ = CbxShape<CI, CO>::LDZ, LDP = CbxShape<CI, CO>::LDP;
+    constexpr int ZSTEP = 256 / (CO / 4);
+    constexpr int LDZ = CbxShape<CI, CO>::LDZ;
     const int R = g.dz.rows;
     const int row0 = tile * TR;
     const int zc4 = (tid % (CO / 4)) * 4, zr = tid / (CO / 4);
-    const int pc4 = (tid % (CI / 4)) * 4, pr = tid / (CI / 4);
 #pragma unroll
     for (int q = 0; q < NZ4; ++q) {
         const int rt = zr + q * ZSTEP;
@@ -846,35 +814,19 @@ __device__ __forceinline__ void cbx_stage(const ConvBwdArgs &g, int tile, int n0
         }
         stage_split_p<TR * LDZ, LDZ>(Zb, rt, CbxShape<CI, CO>::SWZ ? zc4 ^ (((rt >> 2) & 3) << 3) : zc4, v);
     }
-#pragma unroll
-    for (int q = 0; q < (SKIP_PS ? 0 : NP4); ++q) {
-        float4 zp = rp[q];
-        if (RZ1) {
-#pragma clang fp contract(off)
-            const float x0 = rp[q].x, x1 = rp[q].y, x2 = rp[q].z;
-            const float4 c0 = w3[0], c1 = w3[1], c2 = w3[2], c3 = w3[3];
-            zp.x = fmaf(c0.z, x2, fmaf(c0.y, x1, c0.x * x0)) + c0.w;
-            zp.y = fmaf(c1.z, x2, fmaf(c1.y, x1, c1.x * x0)) + c1.w;
-            zp.z = fmaf(c2.z, x2, fmaf(c2.y, x1, c2.x * x0)) + c2.w;
-            zp.w = fmaf(c3.z, x2, fmaf(c3.y, x1, c3.x * x0)) + c3.w;
-        }
-        const float4 a = make_float4(relu_np(fmaf(zp.x, sc4.x, sh4.x)), relu_np(fmaf(zp.y, sc4.y, sh4.y)),
-                                     relu_np(fmaf(zp.z, sc4.z, sh4.z)), relu_np(fmaf(zp.w, sc4.w, sh4.w)));
-        stage_split_p<TR * LDP, LDP>(Pb, pr + q * PSTEP, pc4, a);
-    }
 }
 
-// RZ1 (IN3 only): Zprev is not read -- the producer rebuilds it from the tile's xyz rows (ConvBwdArgs::w_in)
+// RZ1 (IN3 only): Zprev is not read -- its consumers rebuild it from the tile's xyz rows (ConvBwdArgs::w_in)
 // GZ / GP / GW: global row strides (elements) of the dZ-side tensors (Z, dY), of Zprev / dYprev and of W -- a layer with 256 channels on one
 // side runs as two passes of the 128 x 128 instantiation over the halves of that side (the reconstruction sampler's 128 -> 256 -> 128):
 //   256 output channels: the passes take dZ columns / W rows [0,128) and [128,256); the data gradient is their SUM -- DM = 1 (first pass)
 //     stores it raw (no ReLU mask, no statistics), DM = 2 (second) adds ConvBwdArgs::dyacc at the fragment positions before the epilogue;
 //   256 input channels: the passes take W / Zprev / dYprev columns [0,128) and [128,256) and are independent (DM = 0).
-// PW: the activation tile relu(bn(Zprev)) is fetched, activated, split and staged by the WEIGHT-GRADIENT waves (behind their
-//   MFMAs, where they used to wait ~1.5 us per tile at the barrier for the producer waves: tools/timeline.py bwd), the dZ tile
-//   stays with the data-gradient waves -- the serial chain MFMAs -> epilogue -> staging of those waves loses its Zprev half
-template <int CI, int CO, int ZMODE, bool FULLR, bool IN3 = false, bool RZ1 = false, int GZ = CO, int GP = CI, int GW = CI, int DM = 0,
-          bool PW = (SN_CBX_PW != 0) && (!IN3 || (SN_CBX_PW & 2) != 0)>
+// Staging: the data-gradient waves fetch, transform, split and stage the dZ tile; the WEIGHT-GRADIENT waves do the same for the
+//   activation tile relu(bn(Zprev)) (RZ1: rebuilt from the rows' coordinates), behind their MFMAs -- where they would otherwise wait
+//   ~1.5 us per tile at the barrier for the producer waves (tools/timeline.py bwd) while those waves' serial chain MFMAs ->
+//   epilogue -> staging carried both tiles
+template <int CI, int CO, int ZMODE, bool FULLR, bool IN3 = false, bool RZ1 = false, int GZ = CO, int GP = CI, int GW = CI, int DM = 0>
 __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
 {
     static_assert(DM == 0 || (!IN3 && CbxShape<CI, CO>::KS == 1), "two-pass modes: plain 128 x 128 tiles");
@@ -890,8 +842,7 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
     // matrix pipe in this slot) beside the weight-gradient waves' staging of the next activation tile; slot B: the
     // data-gradient epilogue + staging of the next dZ tile beside the weight-gradient MFMAs; one barrier per slot.  In lockstep (one
     // barrier per tile) both groups' MFMAs share the pipe for 1.4 us and then both groups run VALU work with the pipe idle.
-    constexpr bool kSkew = SN_CBX_SKEW != 0 && PW && !IN3 && CI == 128 && CO == 128;
-    constexpr bool kDg2 = SN_CBX_DG2 != 0 || (kSkew && SN_CBX_SKEW_DG2 != 0);
+    constexpr bool kSkew = !IN3 && CI == 128 && CO == 128;
     constexpr int NDW = RB * NCB * KS;
     constexpr int NWT = NOB * NCB / 4;
     constexpr int KD = CO / 16 / KS, KW = TR / 16;  // K = 16 steps of a dgrad wave / of a row tile's wgrad
@@ -913,12 +864,8 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
     const int q0 = dwv * NWT;
     const int cob = q0 / NCB;
     const int G = gridDim.x;
-    // the tiles of a workgroup: a contiguous range (SN_CBX_CONTIG: sequential addresses per workgroup) or every G-th one
-    constexpr bool CT = SN_CBX_CONTIG != 0;
-    const int tpw = (g.ntiles + G - 1) / G;
-    const int tile0 = CT ? (int)blockIdx.x * tpw : (int)blockIdx.x;
-    const int tend = CT ? min(g.ntiles, tile0 + tpw) : g.ntiles;
-    const int tst = CT ? 1 : G;
+    // the tiles of a workgroup: every G-th one (a contiguous range per workgroup measured equal to 6 % slower)
+    const int tile0 = blockIdx.x, tend = g.ntiles, tst = G;
 
     SN_TL(0);
 #ifdef SN_TIMELINE
@@ -934,11 +881,13 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             k2 = *reinterpret_cast<const float4 *>(g.dz.k2 + zc4);
             k3 = *reinterpret_cast<const float4 *>(g.dz.k3 + zc4);
         }
-        const float4 sc4 = *reinterpret_cast<const float4 *>(g.scale_prev + pc4);
-        const float4 sh4 = *reinterpret_cast<const float4 *>(g.shift_prev + pc4);
         const float scd = g.scale_prev[cb * 32 + l31], shd = g.shift_prev[cb * 32 + l31];
         const unsigned qvo = ((rb * 32 + 4 * h) * GP + cb * 32 + l31) * 4;
         const unsigned ovo = ((rb * 32 + (lane >> 3)) * GP + cb * 32 + (lane & 7) * 4) * 4;
+        // (pvo, the Zprev tile's offsets, is read by nothing here: cbf_issue_loads<SKIP_P = true>.  It stays for now because the compiler
+        //  forms zvo differently without this second use of tid / (CO / 4) -- one instruction less in the prologue of the two-pass
+        //  instantiations -- and the change that deleted the activation-tile path from these waves was to leave the device code
+        //  byte for byte as it was.  Replace it by 0u in a change that is measured.)
         const unsigned zvo = ((tid / (CO / 4)) * GZ + zc4) * 4, pvo = ((tid / (CI / 4)) * GP + pc4) * 4, avo = zc4 * 4;
         CbfRsrc rs;
         // (a pass over one half of a 256-channel side starts GZ / 2 or GP / 2 elements into the first row: the last row's range ends
@@ -967,30 +916,21 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         const int tpc = ZMODE == DZ_POOL ? g.dz.npts / TR : 1;
         const int bstep = tst / tpc, tstep = tst - bstep * tpc;
         int cloud = tile0 / tpc, tic = tile0 - cloud * tpc;
-        float4 rz[NZ4], rdy[NZ4], rp[NP4];
+        float4 rz[NZ4], rdy[NZ4], rp[NP4];  // (rp: never loaded here -- cbf_issue_loads<SKIP_P = true>)
         int4 rag = make_int4(0, 0, 0, 0);
         float4 rgs = make_float4(0.f, 0.f, 0.f, 0.f);
         float s0 = 0.f, s1 = 0.f;
-        // RZ1: the xyz layer's weights of the four channels this thread stages and of the channel its dYprev fragment column holds
-        // (w0, w1, w2, bias) per channel of the xyz layer, in LDS behind the coordinate rows: read at every use (20 registers otherwise)
+        // RZ1: (w0, w1, w2, bias) per channel of the xyz layer, in LDS behind the coordinate rows: the epilogue reads the entry of the
+        // channel this lane's dYprev fragment column holds at every use (registers otherwise)
         float4 *W3s = reinterpret_cast<float4 *>(Xs + S::XSZ);
-        constexpr int PSTEPK = 256 / (CI / 4);
-        const unsigned xvo = (tid / (CI / 4)) * 12;
         if (RZ1 && tid < CI)
             W3s[tid] = make_float4(g.w_in[tid * 3], g.w_in[tid * 3 + 1], g.w_in[tid * 3 + 2], g.b_in ? g.b_in[tid] : 0.f);
-        const float4 *w3s = W3s + pc4;
-        // (RZ1) the rows' coordinates in place of the Zprev tile: 12 bytes per row instead of 16 per four channels
-        auto load_xyz_rows = [&](int t) __attribute__((always_inline)) {
-#pragma unroll
-            for (int q = 0; q < NP4; ++q) rp[q] = buf_load3(rsx, xvo, (unsigned)t * (TR * 12) + q * (PSTEPK * 12));
-        };
         float4 vout[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) vout[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 
         int tile = tile0;
-        cbf_issue_loads<CO, CI, TR, ZMODE, NZ4, NP4, RZ1 || PW, GZ, GP>(rs, tile, cloud, zvo, pvo, avo, rz, rdy, rp, rag, rgs);
-        if (RZ1 && !PW) load_xyz_rows(tile);
+        cbf_issue_loads<CO, CI, TR, ZMODE, NZ4, NP4, true, GZ, GP>(rs, tile, cloud, zvo, pvo, avo, rz, rdy, rp, rag, rgs);
         if (xthr) rx = buf_load4(rsx, (unsigned)tid * 16, (unsigned)tile * (TR * 12));
         // W^T fragments of this wave's 32 input channels: W[co = 16 kk + 8 h + t][ci = cb 32 + l31] (requested after the first
         // tile: its staging does not wait for them), split below once the first tile is staged
@@ -1006,8 +946,7 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             k2 = *reinterpret_cast<const float4 *>(Ks + CO + zc4);
             k3 = *reinterpret_cast<const float4 *>(Ks + 2 * CO + zc4);
         }
-        cbx_stage<CO, CI, TR, ZMODE, FULLR, NZ4, NP4, RZ1, PW>(g, tile, tic * TR, tid, Lb, Lb + 3 * ZPL, rz, rdy, rp, rag, rgs, k1, k2, k3, sc4,
-                                                               sh4, w3s);
+        cbx_stage<CO, CI, TR, ZMODE, FULLR, NZ4>(g, tile, tic * TR, tid, Lb, rz, rdy, rag, rgs, k1, k2, k3);
         if (xthr) Xs[xslot[0]] = rx.x, Xs[xslot[1]] = rx.y, Xs[xslot[2]] = rx.z, Xs[xslot[3]] = rx.w;
         bf16x8 wf[KD][3];
 #pragma unroll
@@ -1023,21 +962,21 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             const __bf16 *Zb = Lb + (it & 1) * BUF;
             // the previous tile's dYprev leaves at the top of the iteration.  (The register allocator gives the accumulator the registers
             // of `vout`, dead once stored, so the first MFMA waits for the four stores' acknowledgements -- s_waitcnt vmcnt on a store-data
-            // hazard.  SN_CBX_LATE_ST=1 issues them behind the first k-step's MFMAs instead, from registers of their own: measured, and
-            // not faster -- the write-back L2 acknowledges at once.)
+            // hazard.  Issuing them behind the first k-step's MFMAs instead, from registers of their own, was measured and was not faster
+            // (128 x 128 772 -> 765 us, 64 -> 128 616 -> 648, 64 x 64 376 -> 395 at B = 2048): the write-back L2 acknowledges at once.)
             const auto store_prev = [&]() __attribute__((always_inline)) {
-                if (!IN3 && it > 0 && kh == 0 && SN_CBX_ABL != 3) {
+                if (!IN3 && it > 0 && kh == 0) {
                     const unsigned oso = (unsigned)(tile - tst) * (TR * GP * 4);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) buf_store4<SN_ST_DY>(vout[i], rs.dyprev, ovo, oso + i * (8 * GP * 4));
                 }
             };
-            if (!SN_CBX_LATE_ST || SN_CBX_ABL == 1) store_prev();
+            store_prev();
             float zq[16], pq[16];
             if (!RZ1 && DM != 1 && (KS == 1 || kh == 0))
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
-                    zq[e] = SN_CBX_ABL == 6 ? 1.0f : buf_load1(rs.zprev, qvo, (unsigned)tile * (TR * GP * 4) + ((e & 3) + 8 * (e >> 2)) * (GP * 4));
+                    zq[e] = buf_load1(rs.zprev, qvo, (unsigned)tile * (TR * GP * 4) + ((e & 3) + 8 * (e >> 2)) * (GP * 4));
             if (DM == 2)  // the first pass's raw data gradient at this lane's fragment positions
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
@@ -1049,53 +988,36 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
                 ncloud += bstep, ntic += tstep;
                 if (ntic >= tpc) ntic -= tpc, ++ncloud;
             }
-            cbf_issue_loads<CO, CI, TR, ZMODE, NZ4, NP4, RZ1 || PW, GZ, GP>(rs, nxt, ncloud, zvo, pvo, avo, rz, rdy, rp, rag, rgs);
-            if (RZ1 && !PW) load_xyz_rows(nxt);
+            cbf_issue_loads<CO, CI, TR, ZMODE, NZ4, NP4, true, GZ, GP>(rs, nxt, ncloud, zvo, pvo, avo, rz, rdy, rp, rag, rgs);
             if (xthr) rx = buf_load4(rsx, (unsigned)tid * 16, (unsigned)nxt * (TR * 12));
             // the requests go out HERE: left alone, the scheduler sinks them below the MFMAs to their first use (the staging),
             // and every tile pays a full memory round trip
             __builtin_amdgcn_sched_barrier(0);
             if (it == 1) SN_TL(5);
 
-            // two accumulator chains (even / odd k-steps, added at the end): one chain of KD x 6 dependent MFMAs issues at the
-            // accumulator's latency (~70 cycles apiece, 1.4 us per 128-channel tile: tools/timeline.py bwd), not at the pipe's rate
-            f32x16 acc, acc2;
+            // ONE accumulator chain of KD x 6 dependent MFMAs (1.4 us per 128-channel tile: tools/timeline.py bwd).  Two chains (even / odd
+            // k-steps, added at the end) measured equal -- 939 vs 945 us at B = 2048, 21.3 vs 21.5 at B = 32, the skewed kernel 795 vs
+            // 784-794 us: one chain issues at the pipe's rate (tools/micro/mfma_bf16_chain.hip)
+            f32x16 acc;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f, acc2[e] = 0.f;
+            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
             // (SWZ: slot 2 kk + h of the row sits at slot (2 kk + h) ^ f, f = (row / 4) % 4: two base pointers, even and odd k-steps)
             const int fsw = S::SWZ ? ((l31 >> 2) & 3) ^ h : 0;
             const __bf16 *apr = Zb + (rb * 32 + l31) * LDZ + kh * KD * 16;
             const __bf16 *ape = S::SWZ ? apr + (fsw << 3) : apr + 8 * h, *apo = S::SWZ ? apr + ((fsw ^ 2) << 3) : apr + 8 * h + 16;
 #pragma unroll
-            for (int kk = 0; kk < (SN_CBX_ABL == 1 ? 0 : KD); ++kk) {
+            for (int kk = 0; kk < KD; ++kk) {
                 const __bf16 *ap = ((kk & 1) ? apo : ape) + (kk >> 1) * 32;
                 const bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(ap);
                 const bf16x8 a1 = *reinterpret_cast<const bf16x8 *>(ap + ZPL);
                 const bf16x8 a2 = *reinterpret_cast<const bf16x8 *>(ap + 2 * ZPL);
-                if (kDg2 && (kk & 1)) {
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][2], acc2, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, wf[kk][0], acc2, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][1], acc2, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][1], acc2, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][0], acc2, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][0], acc2, 0, 0, 0);
-                } else {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, wf[kk][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][0], acc, 0, 0, 0);
-                }
-                if (SN_CBX_LATE_ST && kk == 0) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    store_prev();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, wf[kk][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, wf[kk][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wf[kk][0], acc, 0, 0, 0);
             }
-            if (kDg2)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[e] += acc2[e];
             if (it == 1) SN_TL(1);
             if (kSkew) __syncthreads();  // end of slot A
             if (KS == 2) {  // the upper K range's partial tile joins the lower one's through the upper wave's scratch
@@ -1108,66 +1030,65 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[e] += Tx[e * 64 + lane];
             }
-            if (kh == 0 && SN_CBX_ABL != 5) {
-            if (RZ1) {  // Zprev at the fragment positions from the tile's coordinates in LDS (rows 4 q .. 4 q + 3 of a fragment are consecutive)
+            if (kh == 0) {
+                if (RZ1) {  // Zprev at the fragment positions from the tile's coordinates in LDS (rows 4 q .. 4 q + 3 of a fragment are consecutive)
 #pragma clang fp contract(off)  // bit for bit the stored tensor: the bias add must not fuse with what consumes z below
-                const float4 wd = W3s[cb * 32 + l31];
-                const float w3d0 = wd.x, w3d1 = wd.y, w3d2 = wd.z, b3d = wd.w;
-                const float *xq = Xs + (it & 1) * (3 * TR) + rb * 32 + 4 * h;
+                    const float4 wd = W3s[cb * 32 + l31];
+                    const float w3d0 = wd.x, w3d1 = wd.y, w3d2 = wd.z, b3d = wd.w;
+                    const float *xq = Xs + (it & 1) * (3 * TR) + rb * 32 + 4 * h;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 x0 = *reinterpret_cast<const float4 *>(xq + 8 * q);
-                    const float4 x1 = *reinterpret_cast<const float4 *>(xq + TR + 8 * q);
-                    const float4 x2 = *reinterpret_cast<const float4 *>(xq + 2 * TR + 8 * q);
-                    zq[4 * q + 0] = fmaf(w3d2, x2.x, fmaf(w3d1, x1.x, w3d0 * x0.x)) + b3d;
-                    zq[4 * q + 1] = fmaf(w3d2, x2.y, fmaf(w3d1, x1.y, w3d0 * x0.y)) + b3d;
-                    zq[4 * q + 2] = fmaf(w3d2, x2.z, fmaf(w3d1, x1.z, w3d0 * x0.z)) + b3d;
-                    zq[4 * q + 3] = fmaf(w3d2, x2.w, fmaf(w3d1, x1.w, w3d0 * x0.w)) + b3d;
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 x0 = *reinterpret_cast<const float4 *>(xq + 8 * q);
+                        const float4 x1 = *reinterpret_cast<const float4 *>(xq + TR + 8 * q);
+                        const float4 x2 = *reinterpret_cast<const float4 *>(xq + 2 * TR + 8 * q);
+                        zq[4 * q + 0] = fmaf(w3d2, x2.x, fmaf(w3d1, x1.x, w3d0 * x0.x)) + b3d;
+                        zq[4 * q + 1] = fmaf(w3d2, x2.y, fmaf(w3d1, x1.y, w3d0 * x0.y)) + b3d;
+                        zq[4 * q + 2] = fmaf(w3d2, x2.z, fmaf(w3d1, x1.z, w3d0 * x0.z)) + b3d;
+                        zq[4 * q + 3] = fmaf(w3d2, x2.w, fmaf(w3d1, x1.w, w3d0 * x0.w)) + b3d;
+                    }
                 }
-            }
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (DM == 1) {  // first of two passes over the output channels: the raw partial sum
-                    Ts[frag_row(e, lane) * 36 + l31] = acc[e];
-                    continue;
+                for (int e = 0; e < 16; ++e) {
+                    if (DM == 1) {  // first of two passes over the output channels: the raw partial sum
+                        Ts[frag_row(e, lane) * 36 + l31] = acc[e];
+                        continue;
+                    }
+                    const float z = zq[e];
+                    const float a = DM == 2 ? acc[e] + pq[e] : acc[e];
+                    const float v = fmaf(z, scd, shd) > 0.f ? a : 0.f;
+                    s0 += v;
+                    s1 = fmaf(v, z, s1);  // (explicit: the variants of this kernel must round the sum the same way)
+                    if (IN3) acc[e] = v;
+                    if (!IN3) Ts[frag_row(e, lane) * 36 + l31] = v;
                 }
-                const float z = zq[e];
-                const float a = DM == 2 ? acc[e] + pq[e] : acc[e];
-                const float v = fmaf(z, scd, shd) > 0.f ? a : 0.f;
-                s0 += v;
-                s1 = fmaf(v, z, s1);  // (explicit: the variants of this kernel must round the sum the same way)
-                if (IN3) acc[e] = v;
-                if (!IN3) Ts[frag_row(e, lane) * 36 + l31] = v;
-            }
-            if (IN3) {
-                const float *Xc = Xs + (it & 1) * (3 * TR);
-                const float *xp = Xc + rb * 32 + 4 * h;
+                if (IN3) {
+                    const float *Xc = Xs + (it & 1) * (3 * TR);
+                    const float *xp = Xc + rb * 32 + 4 * h;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 x0 = *reinterpret_cast<const float4 *>(xp + 8 * q);
-                    const float4 x1 = *reinterpret_cast<const float4 *>(xp + TR + 8 * q);
-                    const float4 x2 = *reinterpret_cast<const float4 *>(xp + 2 * TR + 8 * q);
-                    gx0 = fmaf(acc[4 * q + 3], x0.w, fmaf(acc[4 * q + 2], x0.z, fmaf(acc[4 * q + 1], x0.y, fmaf(acc[4 * q], x0.x, gx0))));
-                    gx1 = fmaf(acc[4 * q + 3], x1.w, fmaf(acc[4 * q + 2], x1.z, fmaf(acc[4 * q + 1], x1.y, fmaf(acc[4 * q], x1.x, gx1))));
-                    gx2 = fmaf(acc[4 * q + 3], x2.w, fmaf(acc[4 * q + 2], x2.z, fmaf(acc[4 * q + 1], x2.y, fmaf(acc[4 * q], x2.x, gx2))));
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 x0 = *reinterpret_cast<const float4 *>(xp + 8 * q);
+                        const float4 x1 = *reinterpret_cast<const float4 *>(xp + TR + 8 * q);
+                        const float4 x2 = *reinterpret_cast<const float4 *>(xp + 2 * TR + 8 * q);
+                        gx0 = fmaf(acc[4 * q + 3], x0.w, fmaf(acc[4 * q + 2], x0.z, fmaf(acc[4 * q + 1], x0.y, fmaf(acc[4 * q], x0.x, gx0))));
+                        gx1 = fmaf(acc[4 * q + 3], x1.w, fmaf(acc[4 * q + 2], x1.z, fmaf(acc[4 * q + 1], x1.y, fmaf(acc[4 * q], x1.x, gx1))));
+                        gx2 = fmaf(acc[4 * q + 3], x2.w, fmaf(acc[4 * q + 2], x2.z, fmaf(acc[4 * q + 1], x2.y, fmaf(acc[4 * q], x2.x, gx2))));
+                    }
+                    if (wave == 0) {
+                        const float a = Xc[lane], b = Xc[TR + lane], c = Xc[2 * TR + lane];
+                        mom[0] += a, mom[1] += b, mom[2] += c;
+                        mom[3] = fmaf(a, a, mom[3]), mom[4] = fmaf(a, b, mom[4]), mom[5] = fmaf(a, c, mom[5]);
+                        mom[6] = fmaf(b, b, mom[6]), mom[7] = fmaf(b, c, mom[7]), mom[8] = fmaf(c, c, mom[8]);
+                    }
                 }
-                if (wave == 0) {
-                    const float a = Xc[lane], b = Xc[TR + lane], c = Xc[2 * TR + lane];
-                    mom[0] += a, mom[1] += b, mom[2] += c;
-                    mom[3] = fmaf(a, a, mom[3]), mom[4] = fmaf(a, b, mom[4]), mom[5] = fmaf(a, c, mom[5]);
-                    mom[6] = fmaf(b, b, mom[6]), mom[7] = fmaf(b, c, mom[7]), mom[8] = fmaf(c, c, mom[8]);
-                }
-            }
-            if (!IN3) {
+                if (!IN3) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) vout[i] = *reinterpret_cast<const float4 *>(Ts + (8 * i + (lane >> 3)) * 36 + (lane & 7) * 4);
-            }
+                    for (int i = 0; i < 4; ++i) vout[i] = *reinterpret_cast<const float4 *>(Ts + (8 * i + (lane >> 3)) * 36 + (lane & 7) * 4);
+                }
             }
             if (it == 1) SN_TL(2);
-            if (more && SN_CBX_ABL != 4) {
+            if (more) {
                 __bf16 *Zn = Lb + ((it + 1) & 1) * BUF;
-                cbx_stage<CO, CI, TR, ZMODE, FULLR, NZ4, NP4, RZ1, PW>(g, nxt, ntic * TR, tid, Zn, Zn + 3 * ZPL, rz, rdy, rp, rag, rgs, k1, k2,
-                                                                       k3, sc4, sh4, w3s);
+                cbx_stage<CO, CI, TR, ZMODE, FULLR, NZ4>(g, nxt, ntic * TR, tid, Zn, rz, rdy, rag, rgs, k1, k2, k3);
                 if (xthr) {
                     float *Xn = Xs + ((it + 1) & 1) * (3 * TR);
                     Xn[xslot[0]] = rx.x, Xn[xslot[1]] = rx.y, Xn[xslot[2]] = rx.z, Xn[xslot[3]] = rx.w;
@@ -1209,16 +1130,15 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         }
     } else {
         // ---------------- weight-gradient waves ----------------------------------------------------------
-        // (PW) this thread's part of the Zprev tile: 4 channels x NP4 rows, as the producer waves map theirs
+        // this thread's part of the Zprev tile: 4 channels x NP4 rows, mapped as the producer waves map their dZ tile
         constexpr int PSTEPW = 256 / (CI / 4);
         const int tw = tid - 256;
         const int pc4w = (tw % (CI / 4)) * 4, prw = tw / (CI / 4);
         const unsigned pvow = (prw * GP + pc4w) * 4;
         const sn_rsrc rzp = make_rsrc(g.zprev, (unsigned)R * GP * 4);
-        // two register sets: tile t + 2 is requested while tile t + 1 waits to be staged (the kernel moves ~48 KB per tile and CU;
-        // with one tile in flight per CU the chip's HBM latency x bytes-in-flight product tops out near 3.6 TB/s)
-        constexpr int PD = SN_CBX_PD;
-        float4 rpw[PD][NP4];
+        // one register set: tile t + 1 is requested at the top of tile t's iteration and staged behind its MFMAs (a second set, tile t + 2
+        // requested while t + 1 waits, measured SLOWER: 909 -> 1050 us at B = 2048)
+        float4 rpw[NP4];
         float4 scw = make_float4(0.f, 0.f, 0.f, 0.f), shw = scw;
         // RZ1: the rows' coordinates (12 bytes per row) in place of the Zprev tile, and the xyz layer's (w0, w1, w2, bias) of this
         // thread's four channels in registers (the weight-gradient waves of this layer hold one accumulator tile: room to spare)
@@ -1227,24 +1147,24 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         float4 w3w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) w3w[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (PW && RZ1) {
+        if (RZ1) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 w3w[j] = make_float4(g.w_in[(pc4w + j) * 3], g.w_in[(pc4w + j) * 3 + 1], g.w_in[(pc4w + j) * 3 + 2], g.b_in ? g.b_in[pc4w + j] : 0.f);
         }
-        auto load_p = [&](int t, int s) __attribute__((always_inline)) {
+        auto load_p = [&](int t) __attribute__((always_inline)) {
 #pragma unroll
             for (int q = 0; q < NP4; ++q)
-                rpw[s][q] = RZ1 ? buf_load3(rsxw, xvow, (unsigned)t * (TR * 12) + q * (PSTEPW * 12))
-                                : buf_load4(rzp, pvow, (unsigned)t * (TR * GP * 4) + q * (PSTEPW * GP * 4));
+                rpw[q] = RZ1 ? buf_load3(rsxw, xvow, (unsigned)t * (TR * 12) + q * (PSTEPW * 12))
+                             : buf_load4(rzp, pvow, (unsigned)t * (TR * GP * 4) + q * (PSTEPW * GP * 4));
         };
-        auto stage_p = [&](__bf16 *Pb, int s) __attribute__((always_inline)) {
+        auto stage_p = [&](__bf16 *Pb) __attribute__((always_inline)) {
 #pragma unroll
             for (int q = 0; q < NP4; ++q) {
-                float4 zp = rpw[s][q];
-                if (RZ1) {  // the xyz kernel's own expression, bit for bit (cbx_stage's RZ1 branch)
+                float4 zp = rpw[q];
+                if (RZ1) {  // the xyz kernel's own expression, bit for bit (conv_in3_fwd_kernel)
 #pragma clang fp contract(off)
-                    const float x0 = rpw[s][q].x, x1 = rpw[s][q].y, x2 = rpw[s][q].z;
+                    const float x0 = rpw[q].x, x1 = rpw[q].y, x2 = rpw[q].z;
                     zp.x = fmaf(w3w[0].z, x2, fmaf(w3w[0].y, x1, w3w[0].x * x0)) + w3w[0].w;
                     zp.y = fmaf(w3w[1].z, x2, fmaf(w3w[1].y, x1, w3w[1].x * x0)) + w3w[1].w;
                     zp.z = fmaf(w3w[2].z, x2, fmaf(w3w[2].y, x1, w3w[2].x * x0)) + w3w[2].w;
@@ -1255,12 +1175,9 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
                 stage_split_p<TR * LDP, LDP>(Pb, prw + q * PSTEPW, pc4w, a);
             }
         };
-        if (PW) {
-            load_p(tile0, 0);
-            if (PD == 2) load_p(min(tile0 + tst, g.ntiles - 1), 1);
-            scw = *reinterpret_cast<const float4 *>(g.scale_prev + pc4w);
-            shw = *reinterpret_cast<const float4 *>(g.shift_prev + pc4w);
-        }
+        load_p(tile0);
+        scw = *reinterpret_cast<const float4 *>(g.scale_prev + pc4w);
+        shw = *reinterpret_cast<const float4 *>(g.shift_prev + pc4w);
         if (ZMODE == DZ_BN && g.acc_in != nullptr) {
             float *Ks = Tf;
             const int c = tid - 256;
@@ -1284,8 +1201,8 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
         for (int n = 0; n < NWT; ++n)
 #pragma unroll
             for (int e = 0; e < 16; ++e) accw[n][e] = 0.f;
-        if (PW) stage_p(Lb + 3 * ZPL, 0);
-        if (kSkew) load_p(tile0 + tst < tend ? tile0 + tst : tile0, 0);  // (slot A of the first tile stages it)
+        stage_p(Lb + 3 * ZPL);
+        if (kSkew) load_p(tile0 + tst < tend ? tile0 + tst : tile0);  // (slot A of the first tile stages it)
         __syncthreads();
         // transposing reads: this lane's row / channel offsets inside a [16 rows][32 channels] fragment block
         const int trr = 8 * h + ((lane & 15) >> 2), trc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
@@ -1295,19 +1212,14 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             const bool more = tile + tst < tend;
             if (kSkew) {
                 // slot A: the next activation tile (requested one slot ago) into the other buffer, beside the data-gradient MFMAs
-                if (more) stage_p(Lb + ((it + 1) & 1) * BUF + 3 * ZPL, 0);
+                if (more) stage_p(Lb + ((it + 1) & 1) * BUF + 3 * ZPL);
                 if (it == 1) SN_TL(2);
                 __syncthreads();
                 if (it == 1) SN_TL(3);
-                load_p(tile + 2 * tst < tend ? tile + 2 * tst : tile, 0);
+                load_p(tile + 2 * tst < tend ? tile + 2 * tst : tile);
                 __builtin_amdgcn_sched_barrier(0);
-            } else if (PW) {
-                // (PD == 2: set (it + 1) % 2 holds the next tile already; the set this tile's staging freed takes the one after)
-                if (PD == 2) {
-                    if (it & 1) load_p(min(tile + 2 * tst, g.ntiles - 1), 1); else load_p(min(tile + 2 * tst, g.ntiles - 1), 0);
-                } else {
-                    load_p(more ? tile + tst : tile, 0);
-                }
+            } else {
+                load_p(more ? tile + tst : tile);
                 __builtin_amdgcn_sched_barrier(0);  // (the requests leave before the MFMAs, not next to the staging behind them)
             }
             // (SWZ: rows 16 kk + 8 h + 0..3 carry f = 2 h, the rows four below f = 2 h + 1)
@@ -1326,9 +1238,9 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
                     for (int n = 0; n < NWT; ++n) fb[s][p][n] = lds_tr8(bp + p * PPL + kk * 16 * LDP + ((q0 + n) % NCB) * 32, LDP);
                 }
             };
-            if (SN_CBX_ABL != 2) frag_load(0, 0);
+            frag_load(0, 0);
 #pragma unroll
-            for (int kk = 0; kk < (SN_CBX_ABL == 2 ? 0 : KW); ++kk) {
+            for (int kk = 0; kk < KW; ++kk) {
                 if (kk + 1 < KW) frag_load(kk + 1, (kk + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
                 const bf16x8(&a)[3] = fa[kk & 1];
@@ -1346,10 +1258,7 @@ __global__ void __launch_bounds__(512) conv_bwd_bx3_kernel(ConvBwdArgs g)
             }
             if (it == 1) SN_TL(1);
             if (KS == 2) __syncthreads();  // (the dgrad waves' partial-tile hand-off)
-            if (PW && !kSkew && more && SN_CBX_ABL != 4) {
-                if (PD == 2 && !(it & 1)) stage_p(Lb + ((it + 1) & 1) * BUF + 3 * ZPL, 1);
-                else stage_p(Lb + ((it + 1) & 1) * BUF + 3 * ZPL, 0);
-            }
+            if (!kSkew && more) stage_p(Lb + ((it + 1) & 1) * BUF + 3 * ZPL);
             __syncthreads();
             if (it == 1) SN_TL(4);
         }

@@ -73,15 +73,12 @@ inline int sn_lds_attr_grow(SnLdsAttrGrow &a, const void *fn, size_t bytes, cons
     return 0;
 }
 
-// spacing (in 32-bit words) of the words of an FC chain launch's `sync` state: word i lives at sync[i * SN_FC_SYNC_STRIDE]
-// (fc_chain.hip: kFcSyncStride; geometry_ops.hip: the step tail reads the error words)
-#ifndef SN_FC_SYNC_STRIDE
-#define SN_FC_SYNC_STRIDE 32
-#endif
-
 namespace sn {
 
 constexpr int kWave = 64;
+// spacing (in 32-bit words) of the words of an FC chain launch's `sync` state: word i lives at sync[i * kFcSyncStride], 128 bytes
+// apart (fc_chain.hip; geometry_ops.hip: the step tail reads the error words; samplenet_amd/pointnet.py mirrors it as SYNC_STRIDE)
+constexpr int kFcSyncStride = 32;
 constexpr sn_u64 kKeyInf = ~0ull;
 
 // (distance, index) packed so that unsigned order == lexicographic (distance, index) order.

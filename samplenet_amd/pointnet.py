@@ -16,7 +16,7 @@ import torch
 from ._lib import check, lib, ptr, stream_of
 
 DZ_PLAIN, DZ_BN, DZ_POOL = 0, 1, 2
-SYNC_STRIDE = 32  # words between the words of a chain launch's sync state (sn_common.h: SN_FC_SYNC_STRIDE): [i, 0] is word i
+SYNC_STRIDE = 32  # words between the words of a chain launch's sync state (sn_common.h: kFcSyncStride): [i, 0] is word i
 
 
 def _st(t):

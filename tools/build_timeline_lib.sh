@@ -6,7 +6,7 @@ set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/_ab
 L=${LEVEL:-1}
-X=${EXTRA:-}          # extra flags for the MLP unit (e.g. EXTRA="-DSN_CBX_SKEW=1")
+X=${EXTRA:-}          # extra flags for the MLP unit (e.g. EXTRA="-DSN_ST_Z=0")
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Isamplenet_amd/csrc -Wno-unused-function -Xclang -target-feature -Xclang -packed-fp32-ops"
 G="$F -ffp-contract=off -DSN_PS_TIMELINE=$L -DSN_CS_TIMELINE=$L"
 # the four MLP translation units as ONE (the stamp buffers of mlp_device.h then exist once, whichever kernel writes them)
