@@ -1665,7 +1665,8 @@ extern "C" int sn_sampler_step_loss_forward_direct(int B, int M, int N, const fl
     return 0;
 }
 
-// grad_Q (B,3,M) channel-major (the FC head's layout), grad_T (1).  P: (B,N,3) or (B,3,N) by p_layout; Q: (B,3,M).
+// grad_Q (B,3,M) channel-major (the FC head's layout), grad_T (1).  P: (B,N,3) only -- any p_layout but SN_LAYOUT_BNC is refused
+// (the fused kernel loads a point as one 12-byte word); Q: (B,3,M).
 // gsig_scratch: B * sn_soft_bwd_splits(B, M) floats.
 extern "C" int sn_sampler_step_loss_backward(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
                                              const int *knn_idx, const int *idx_q, const int *idx_p, const int *argmax1,

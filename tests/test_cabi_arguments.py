@@ -4,7 +4,8 @@ documented code and its OWN name in sn_last_error_string(), and treats the docum
 any device work.  So do the entries of include/samplenet_hip_internal.h that the task networks share: the skinny FC route
 (sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
 transforms, the orthogonality regulariser and sn_bn_relu_*, and the nine entries of the one-batch task evaluation (cyclic padding, the
-valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped), and the twelve entries of the sampler
+step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 import json
@@ -94,6 +95,45 @@ TASK_BATCH = {
     "sn_chamfer_mean_loss_backward_grouped": ([2, 4, Pp, 8, Pp, 2, 1, HOSTI, Pp, Pp, Pp, None, None, None], [0, 1, 3, 5, 6],
                                               [2, 4, 7, 8, 9, 10]),
 }
+# The sampler step's fused loss entries (include/samplenet_hip_internal.h; tests/test_gpu_step_loss.py calls them on a device), same
+# rules.  Every size is >= 1 here (no empty case documented): 0 is refused like -1.  The scan bases are a shape whose queries are
+# spread over three workgroups (2 clouds of 8 points, 40 queries), so that a refusal cannot be mistaken for the G <= 1 answer.
+STEP_LOSS = {
+    # B, N, M, K, P, p_layout, Q, q_layout, knn_idx, dist_q, idx_q, proj, proj_layout, temperature, min_sigma, workspace, workspace_bytes, stream
+    "sn_pairscan_forward_partial": ([2, 8, 40, 2, Pp, 0, Pp, 0, Pp, Pp, Pp, Pp, 0, Pp, 0.0, Pp, 1 << 20, None], [0, 1, 2, 3], [4, 6, 13, 15]),
+    # B, N, M, K, P, p_layout, fc_z, fc_scale, fc_shift, fc_w, fc_bias, Kfc, q_out, knn_idx, dist_q, idx_q, proj, proj_layout, temperature,
+    # min_sigma, workspace, workspace_bytes, stream
+    "sn_pairscan_forward_partial_fc": ([2, 8, 40, 2, Pp, 0, Pp, Pp, Pp, Pp, Pp, 8, Pp, Pp, Pp, Pp, Pp, 0, Pp, 0.0, Pp, 1 << 20, None],
+                                       [0, 1, 2, 3, 11], [4, 6, 7, 8, 9, 10, 12, 18, 20]),
+    # B, N, M, K, P, p_layout, Q, fc_z, fc_scale, fc_shift, fc_w, fc_bias, Kfc, knn_idx, dist_q, idx_q, proj, proj_layout, temperature,
+    # min_sigma, colmin_keys, qpart, qmax, stream
+    "sn_pairscan_forward_keys": ([2, 8, 40, 2, Pp, 0, Pp, None, None, None, None, None, 0, Pp, Pp, Pp, Pp, 0, Pp, 0.0, Pp, Pp, Pp, None],
+                                 [0, 1, 2, 3], [4, 6, 14, 16, 18, 20, 21, 22]),
+    # B, M, N, G, dist_q, colmin_ws, proj, temperature, alpha, lmbda, weight, min_sigma, dist_p, idx_p, argmax1, partial, loss, defer_value, stream
+    "sn_sampler_step_loss_forward": ([2, 40, 8, 3, Pp, Pp, Pp, Pp, 0.5, 0.5, 1.0, 0.0, Pp, Pp, Pp, Pp, Pp, 0, None], [0, 1, 2, 3],
+                                     [4, 5, 6, 7, 12, 13, 14, 15, 16]),
+    # B, M, N, dist_q, dist_p, proj, temperature, alpha, lmbda, weight, min_sigma, argmax1, partial, loss, defer_value, stream
+    "sn_sampler_step_loss_forward_direct": ([2, 40, 8, Pp, Pp, Pp, Pp, 0.5, 0.5, 1.0, 0.0, Pp, Pp, Pp, 0, None], [0, 1, 2],
+                                            [3, 4, 5, 6, 11, 12, 13]),
+    # B, N, M, K, P, p_layout, Q, knn_idx, idx_q, idx_p, argmax1, temperature, min_sigma, alpha, lmbda, weight, grad_loss, grad_Q,
+    # gsig_scratch, grad_T, deferred_partial, deferred_loss, stream
+    "sn_sampler_step_loss_backward": ([2, 8, 40, 2, Pp, 0, Pp, Pp, Pp, Pp, Pp, Pp, 0.0, 0.5, 0.5, 1.0, Pp, Pp, Pp, Pp, None, None, None],
+                                      [0, 1, 2, 3], [4, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19]),
+    # B, N, M, K, P, p_layout, Q, knn_idx, idx_q, colmin_keys, qpart, qmax, G, temperature, min_sigma, alpha, lmbda, weight, grad_loss, grad_Q,
+    # gsig_scratch, grad_T, dpsum, loss, stream, deferred_tail, grad_proj, grad_sigma
+    "sn_sampler_step_loss_keys": ([2, 8, 40, 2, Pp, 0, Pp, Pp, Pp, Pp, Pp, Pp, 3, Pp, 0.0, 0.5, 0.5, 1.0, Pp, Pp, Pp, Pp, Pp, Pp, None, None,
+                                   None, None], [0, 1, 2, 3, 12], [4, 6, 7, 8, 9, 10, 11, 13, 18, 19, 20, 21, 22, 23]),
+    # B, N, M, G, colmin_keys, qpart, qmax, temperature, min_sigma, weight, y_bcn, simp_bnc, dpsum, values, stream
+    "sn_surface_values_keys": ([2, 8, 40, 3, Pp, Pp, Pp, Pp, 0.0, 1.0, None, None, Pp, Pp, None], [0, 1, 2, 3], [4, 5, 6, 7, 12, 13]),
+    # nproj, g_lsimp, g_sigma, g_proj, scalars, proj_out, stream
+    "sn_surface_gather_upstream": ([24, None, None, None, Pp, Pp, None], [0], [4, 5]),
+    # nproj, proj, lsimp, temperature, alpha, lmbda, min_sigma, loss, stream
+    "sn_sampler_loss_forward": ([24, Pp, Pp, Pp, 0.5, 0.5, 0.0, Pp, None], [0], [1, 2, 3, 7]),
+    # nproj, grad_loss, temperature, alpha, lmbda, min_sigma, grad_proj, grad_lsimp, grad_T, stream
+    "sn_sampler_loss_backward": ([24, Pp, Pp, 0.5, 0.5, 0.0, Pp, Pp, Pp, None], [0], [1, 2, 6, 7, 8]),
+    # temperature, min_sigma, sigma, stream
+    "sn_sigma_forward": ([Pp, 0.0, Pp, None], [], [0, 2]),
+}
 # sn_skinny_linear / sn_skinny_linear2 answer a size they do not serve -- negative ones included -- with UNSUPPORTED (callers ask
 # sn_skinny_linear_supported and take another route), so the generic "negative size is a BAD argument" rule above does not fit them:
 # entry -> (valid argument list, required pointers); every case is spelled out in _skinny_cases().
@@ -106,7 +146,7 @@ SKINNY = {
 
 
 def _with(name, changes):
-    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or SKINNY[name])[0])
+    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -170,7 +210,7 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
-    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases()
+    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases()
 
 
 def _skinny_cases():
@@ -237,6 +277,46 @@ def _task_batch_cases():
     return out
 
 
+def _step_loss_cases():
+    out = []
+    add = lambda cid, name, ch, text=None, code=BAD: out.append(("%s-%s" % (name, cid), name, _with(name, ch), code, text or name))
+    for name, (base, sizes, required) in STEP_LOSS.items():
+        for pos in sizes:
+            add("size%d-negative" % pos, name, {pos: -1})
+            add("size%d-zero" % pos, name, {pos: 0})
+        for pos in required:
+            add("arg%d-null" % pos, name, {pos: None})
+    scans = ("sn_pairscan_forward_partial", "sn_pairscan_forward_partial_fc", "sn_pairscan_forward_keys")
+    for name in scans + ("sn_sampler_step_loss_backward", "sn_sampler_step_loss_keys"):
+        add("K65", name, {1: 100, 3: 65})
+        for bad in (2, -1):
+            add("p_layout-is-%d" % bad, name, {5: bad})
+    for name in scans:
+        add("K-above-N", name, {3: 9})
+    for bad in (2, -1):
+        add("q_layout-is-%d" % bad, scans[0], {7: bad})
+    # the layout refusal: the backward entries take the reference cloud as (B,N,3) only
+    for name in ("sn_sampler_step_loss_backward", "sn_sampler_step_loss_keys"):
+        add("P-channel-major", name, {5: 1}, "(B,N,3)")
+    add("deferred_loss-without-partials", "sn_sampler_step_loss_backward", {21: Pp}, "deferred")
+    add("N2049", "sn_sampler_step_loss_keys", {1: 2049}, "N <= 2048", UNSUP)
+    # Kfc: a multiple of 4, at least 4
+    for kfc in (0, 2, 6, 261):
+        add("Kfc%d" % kfc, scans[1], {11: kfc}, "multiple of 4")
+        add("Kfc%d" % kfc, scans[2], {7: Pp, 8: Pp, 9: Pp, 10: Pp, 11: Pp, 12: kfc}, "bad fc operands")
+    for pos in (7, 8, 9, 11):
+        add("fc_w-without-arg%d" % pos, scans[2], {**{q: Pp for q in (7, 8, 9, 10, 11)}, 12: 8, pos: None}, "bad fc operands")
+    # the partial scans check the workspace before any device work (these bases spread a cloud over 3 workgroups: 2 * 3 * 8 keys)
+    for name, pos in ((scans[0], 16), (scans[1], 21)):
+        add("workspace-one-byte-short", name, {pos: 2 * 3 * 8 * 8 - 1}, "workspace too small")
+        add("workspace-of-0-bytes", name, {pos: 0}, "workspace too small")
+    # a shape that runs as one workgroup per cloud is UNSUPPORTED, whatever the workspace
+    for name in scans:
+        add("one-workgroup-per-cloud", name, {2: 4}, "one workgroup per cloud", UNSUP)
+    add("simp_bnc-without-y_bcn", "sn_surface_values_keys", {11: Pp})
+    return out
+
+
 def _transform_cases(nulled):
     out = []
     tf, tb, of, ob = "sn_cloud_transform_forward", "sn_cloud_transform_backward", "sn_orthogonality_loss_forward", "sn_orthogonality_loss_backward"
@@ -263,7 +343,7 @@ def _transform_cases(nulled):
 
 
 CASES = _cases()
-IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
+IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
                                                "sn_skinny_linear_scratch_bytes"]
 
 _CHILD = r"""
@@ -302,7 +382,7 @@ def results():
 def test_the_table_walks_every_entry_in_scope():
     from samplenet_amd import _lib
 
-    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()):
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()) + list(STEP_LOSS.items()):
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto), name
         for pos, ty in enumerate(proto):
