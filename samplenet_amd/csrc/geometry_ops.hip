@@ -105,10 +105,121 @@ __global__ void __launch_bounds__(256) chamfer_bwd_kernel(int nt, int ns, const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Ordered owner sum of the register-resident kernels below.  The sources whose nearest target is j ("owners") are met slot
+// by slot (slot i = sources i * 64 + lane); the reference adds their contributions one after the other in ascending source
+// index, and so does this -- the same fp32 subtractions in the same order -- but as a chain over lanes instead of a scalar
+// walk (find the lowest set bit, clear it, three v_readlane, three dependent v_sub: ~10 issue slots per owner on a value
+// that is the same in all 64 lanes):
+//   1. every owner's rank among the query's owners = popcount of the earlier slots' ballots + mbcnt of its own; the owners
+//      store their contributions, compacted in that order, into a list of kOwnerCap entries per wave in LDS;
+//   2. the list is read back 16 entries per row of 16 lanes, x / y / z in rows 0 / 1 / 2, and every entry is one link
+//      acc = row_ror:1(acc) - c: lane t's link t + 1 takes the running value from lane t - 1 and subtracts entry t, lane 0
+//      takes it from lane 15 -- the start value, or the end of the chunk before -- so the chunks follow each other without
+//      any hand-over and the sum stands in lane 15 after 16 links (whatever the other lanes hold by then).  Entries past the
+//      end of the list subtract +0, which changes no bit of any value; the last chunk stops after its own entries (rounded
+//      up to 4 links) and the sum is taken from the lane it has reached.
+// The list is drained when the slots are through, not per slot (one owner per slot is the usual case and an LDS round trip
+// per slot would cost more than the walk it replaces); a query can own every source, so the list is bounded and the slots are
+// passed once more per kOwnerCap owners.
+// ------------------------------------------------------------------------------------------------
+constexpr int kOwnerCap = 256;            // entries of a wave's list, a multiple of 16 (the headline's busiest queries own ~120 points)
+constexpr int kOwnerRow = kOwnerCap + 16;  // one coordinate's row: the entries, then 16 words that take the stores of owners past the
+                                           // capacity in the first pass and the (masked-off) read of a chunk behind the last one
+struct OwnerList {
+    float c[3][kOwnerRow];
+};
+
+__device__ __forceinline__ float dpp_row_ror1(float x)  // lane below within the row of 16; the row's lane 0 reads its lane 15
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x121, 0xf, 0xf, true));
+}
+
+// (ax, ay, az) -> ((a - c_o0) - c_o1) - ... over the owners o0 < o1 < ... of target j, c_o = gg_o (s_o - t); wave-uniform in and out
+template <int PPL>
+__device__ __forceinline__ void owner_sum(OwnerList &L, int lane, int j, const int (&is)[PPL], const float (&gg)[PPL],
+                                          const float (&sx)[PPL], const float (&sy)[PPL], const float (&sz)[PPL], float tx,
+                                          float ty, float tz, float &ax, float &ay, float &az)
+{
+    const int row = lane >> 4, sub = lane & 15;
+    const float *col = &L.c[row < 3 ? row : 2][sub];  // (row 3 idles along row 2)
+    float acc = row == 0 ? ax : (row == 1 ? ay : az);
+    int at = 15;  // lane of every row that holds the sum
+    auto drain = [&](int cnt) {  // the chain over the first cnt entries of the list
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the list: written by other lanes of this wave
+        float v = sub < cnt ? col[0] : 0.f;
+#pragma nounroll
+        for (int c0 = 0; c0 < cnt; c0 += 16) {
+            const int e = c0 + 16 + sub;  // the next chunk is on its way while this one's chain runs
+            const float vn = e < cnt ? col[c0 + 16] : 0.f;
+            const int rem = cnt - c0;
+            if (rem >= 16) {
+#pragma unroll
+                for (int t = 0; t < 16; ++t) acc = dpp_row_ror1(acc) - v;
+            } else {  // the last chunk of all
+#pragma nounroll
+                for (int t = 0; t < rem; t += 4) {
+                    acc = dpp_row_ror1(acc) - v;
+                    acc = dpp_row_ror1(acc) - v;
+                    acc = dpp_row_ror1(acc) - v;
+                    acc = dpp_row_ror1(acc) - v;
+                }
+                at = ((rem + 3) & ~3) - 1;
+            }
+            v = vn;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        // nothing is in flight here, but the compiler counts the masked-off read of a chunk behind the last one as pending and
+        // would wait for the LDS queue -- the stores of the slot before -- in every slot of the next pass or query
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+    };
+    // the first pass over the slots lists the owners of rank 0 .. kOwnerCap - 1 (those past it store into the row's spare words)
+    int total = 0;  // owners in the slots so far
+#pragma unroll
+    for (int i = 0; i < PPL; ++i) {
+        const bool own = is[i] == j;
+        const sn_u64 mask = __ballot(own);
+        if (mask) {
+            // (a product of its own: no fma may absorb it into the chain's subtraction)
+            const float cx = gg[i] * (sx[i] - tx), cy = gg[i] * (sy[i] - ty), cz = gg[i] * (sz[i] - tz);
+            const unsigned r = total + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            const unsigned rc = r < (unsigned)kOwnerCap ? r : (unsigned)kOwnerCap;
+            if (own) L.c[0][rc] = cx, L.c[1][rc] = cy, L.c[2][rc] = cz;
+            total += __builtin_popcountll(mask);
+        }
+    }
+    drain(total < kOwnerCap ? total : kOwnerCap);
+    // a query with more owners (rare: the mean is ns / nt) takes one further pass and chain per kOwnerCap of them
+#pragma nounroll
+    for (int base = kOwnerCap; base < total; base += kOwnerCap) {
+        // (opaque to the compiler: otherwise it forms the ballots and contributions of ALL slots ahead of this loop and keeps them,
+        //  2 PPL scalar and 3 PPL vector registers)
+        j = __builtin_amdgcn_readfirstlane(j);  // (wave-uniform already; a scalar register whatever the compiler made of it)
+        asm volatile("" : "+v"(tx), "+v"(ty), "+v"(tz), "+s"(j));
+        int n = 0;
+#pragma unroll
+        for (int i = 0; i < PPL; ++i) {
+            const bool own = is[i] == j;
+            const sn_u64 mask = __ballot(own);
+            if (mask) {
+                const int n0 = n;
+                n += __builtin_popcountll(mask);
+                if (n > base && n0 < base + kOwnerCap) {
+                    const float cx = gg[i] * (sx[i] - tx), cy = gg[i] * (sy[i] - ty), cz = gg[i] * (sz[i] - tz);
+                    const int r = n0 - base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+                    if (own && (unsigned)r < (unsigned)kOwnerCap) L.c[0][r] = cx, L.c[1][r] = cy, L.c[2][r] = cz;
+                }
+            }
+        }
+        drain(total - base < kOwnerCap ? total - base : kOwnerCap);
+    }
+    ax = readlane_f(acc, at), ay = readlane_f(acc, 16 + at), az = readlane_f(acc, 32 + at);
+}
+
 // Register-resident variant for ns <= 64*PPL (the sampler's 1024-point clouds): every lane loads its PPL sources
 // (coordinates, nearest-target index, upstream gradient) ONCE, all loads in flight together; per target the matching
 // lanes form their contribution in parallel and only the ordered accumulation (ascending source index, as the
-// reference CPU loop) is sequential -- on registers via v_readlane, no memory latency inside it.
+// reference CPU loop) is sequential -- owner_sum above, no memory latency inside it.
 template <int PPL>
 __global__ void __launch_bounds__(256) chamfer_bwd_reg_kernel(int nt, int ns, const float *__restrict__ T,
                                                               const float *__restrict__ S,
@@ -118,6 +229,7 @@ __global__ void __launch_bounds__(256) chamfer_bwd_reg_kernel(int nt, int ns, co
                                                               const int *__restrict__ idxS, float *__restrict__ gradT,
                                                               int own_first, ImplicitGrad ig, int t_layout)
 {
+    __shared__ OwnerList s_own[4];  // one per wave (256 threads)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
@@ -158,20 +270,7 @@ __global__ void __launch_bounds__(256) chamfer_bwd_reg_kernel(int nt, int ns, co
         const float oz = g * (tz - S[j2 * 3 + 2]);
         float ax = 0.f, ay = 0.f, az = 0.f;
         if (own_first) ax += ox, ay += oy, az += oz;
-#pragma unroll
-        for (int i = 0; i < PPL; ++i) {
-            sn_u64 mask = __ballot(is[i] == j);
-            if (mask) {
-                const float cx = gg[i] * (sx[i] - tx), cy = gg[i] * (sy[i] - ty), cz = gg[i] * (sz[i] - tz);
-                while (mask) {  // ascending source index: lanes of slot i in lane order, slots in order
-                    const int t = __builtin_ctzll(mask);
-                    mask &= mask - 1;
-                    ax -= readlane_f(cx, t);
-                    ay -= readlane_f(cy, t);
-                    az -= readlane_f(cz, t);
-                }
-            }
-        }
+        owner_sum<PPL>(s_own[wave], lane, j, is, gg, sx, sy, sz, tx, ty, tz, ax, ay, az);
         if (!own_first) ax += ox, ay += oy, az += oz;
         if (lane < 3) gradT[o0 + lane * os] = lane == 0 ? ax : (lane == 1 ? ay : az);
     }
@@ -652,9 +751,28 @@ __device__ unsigned long long g_cs_tl[8192 * 16];
 #else
 #define CS_TL_DRAIN()
 #endif
+// ... and lane 0 of EVERY wave records the longest ordered owner sum among its queries (ticks; the operands have landed before
+// the first stamp and the sum is complete before the second, at either level)
+__device__ unsigned g_cs_walk[8192 * 4];
+#define CS_WALK_BEGIN()                                              \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+    const unsigned long long walk_t0 = wall_clock64()
+#define CS_WALK_END(x, y, z)                                                                          \
+    do {                                                                                              \
+        asm volatile("; owner sum done" ::"v"(x), "v"(y), "v"(z) : "memory");                         \
+        const unsigned walk_dt = (unsigned)(wall_clock64() - walk_t0);                                \
+        walk_max = walk_dt > walk_max ? walk_dt : walk_max;                                           \
+    } while (0)
+#define CS_WALK_STORE()                                                                                                   \
+    do {                                                                                                                  \
+        if (lane == 0) g_cs_walk[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 4 + wave] = walk_max + 1u; /* 0 = no query */ \
+    } while (0)
 #else
 #define CS_TL(slot)
 #define CS_TL_DRAIN()
+#define CS_WALK_BEGIN()
+#define CS_WALK_END(x, y, z)
+#define CS_WALK_STORE()
 #endif
 
 template <int PPL>
@@ -668,6 +786,7 @@ __global__ void __launch_bounds__(256) chamfer_soft_bwd_kernel(int nt, int ns, c
     __shared__ int s_ip[PPL * 64];
     __shared__ float s_red[3][4];
     __shared__ int s_am;
+    __shared__ OwnerList s_own[4];  // one per wave
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
@@ -775,6 +894,9 @@ __global__ void __launch_bounds__(256) chamfer_soft_bwd_kernel(int nt, int ns, c
     CS_TL(1);
     const int amt = fold.keys ? s_am : (ig.argmax_t ? ig.argmax_t[b] : -1), ams = ig.argmax_s ? ig.argmax_s[b] : -1;
     float gsig = 0.f;
+#ifdef SN_CS_TIMELINE
+    unsigned walk_max = 0;
+#endif
 #pragma unroll
     for (int i = 0; i < PPL; ++i) {
         const int l = i * 64 + lane;
@@ -793,20 +915,9 @@ __global__ void __launch_bounds__(256) chamfer_soft_bwd_kernel(int nt, int ns, c
         const float g = gLv * (ig.ct + (j == amt ? ig.cmax_t : 0.f)) * 2;
         float ax = g * (tx - ox), ay = g * (ty - oy), az = g * (tz - oz);  // own term first
         if (j == (int)blockIdx.y * nwaves) { CS_TL_DRAIN(); CS_TL(3); }
-#pragma unroll
-        for (int i = 0; i < PPL; ++i) {
-            sn_u64 mask = __ballot(is[i] == j);
-            if (mask) {
-                const float cx = gg[i] * (sx[i] - tx), cy = gg[i] * (sy[i] - ty), cz = gg[i] * (sz[i] - tz);
-                while (mask) {
-                    const int t = __builtin_ctzll(mask);
-                    mask &= mask - 1;
-                    ax -= readlane_f(cx, t);
-                    ay -= readlane_f(cy, t);
-                    az -= readlane_f(cz, t);
-                }
-            }
-        }
+        CS_WALK_BEGIN();
+        owner_sum<PPL>(s_own[wave], lane, j, is, gg, sx, sy, sz, tx, ty, tz, ax, ay, az);
+        CS_WALK_END(ax, ay, az);
         if (j == (int)blockIdx.y * nwaves) CS_TL(4);
         float qx, qy, qz, asg;
         soft_bwd_math<true>(sa, b, j, lane, sigma, sq, qx, qy, qz, asg);
@@ -821,6 +932,7 @@ __global__ void __launch_bounds__(256) chamfer_soft_bwd_kernel(int nt, int ns, c
         for (int w2 = 0; w2 < nwaves; ++w2) tot += s_part[w2];
         sa.grad_sigma_partial[(size_t)b * nsplit + blockIdx.y] = tot;
     }
+    if (jfirst < nt) CS_WALK_STORE();
     CS_TL_DRAIN();
     CS_TL(6);
 }
@@ -1050,6 +1162,7 @@ __global__ void __launch_bounds__(256) chamfer_bwd_grouped_kernel(int nt, int ns
                                                                   const int *__restrict__ idxT, const int *__restrict__ idxS,
                                                                   float *__restrict__ gradT, int own_first, GroupedGrad gg)
 {
+    __shared__ OwnerList s_own[4];  // one per wave
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
@@ -1084,20 +1197,7 @@ __global__ void __launch_bounds__(256) chamfer_bwd_grouped_kernel(int nt, int ns
         const float oz = g * (tz - S[j2 * 3 + 2]);
         float ax = 0.f, ay = 0.f, az = 0.f;
         if (own_first) ax += ox, ay += oy, az += oz;
-#pragma unroll
-        for (int i = 0; i < PPL; ++i) {
-            sn_u64 mask = __ballot(is[i] == j);
-            if (mask) {
-                const float cx = gs2[i] * (sx[i] - tx), cy = gs2[i] * (sy[i] - ty), cz = gs2[i] * (sz[i] - tz);
-                while (mask) {
-                    const int t = __builtin_ctzll(mask);
-                    mask &= mask - 1;
-                    ax -= readlane_f(cx, t);
-                    ay -= readlane_f(cy, t);
-                    az -= readlane_f(cz, t);
-                }
-            }
-        }
+        owner_sum<PPL>(s_own[wave], lane, j, is, gs2, sx, sy, sz, tx, ty, tz, ax, ay, az);
         if (!own_first) ax += ox, ay += oy, az += oz;
         if (lane < 3) gradT[j * 3 + lane] = lane == 0 ? ax : (lane == 1 ? ay : az);
     }
@@ -2717,5 +2817,14 @@ extern "C" int sn_debug_chamfer_soft_bwd_timeline(void *host, int nblocks)
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cs_tl), (size_t)nblocks * 16 * 8) != hipSuccess) return -3;
     static unsigned long long zeros[8192 * 16];
     return hipMemcpyToSymbol(HIP_SYMBOL(g_cs_tl), zeros, sizeof(zeros)) == hipSuccess ? 0 : -4;
+}
+// ... the per-wave owner-sum durations of the first nblocks workgroups (nblocks x 4 words: ticks + 1, 0 = the wave had no query)
+extern "C" int sn_debug_chamfer_soft_bwd_walk(void *host, int nblocks)
+{
+    if (nblocks < 0 || nblocks > 8192) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cs_walk), (size_t)nblocks * 4 * 4) != hipSuccess) return -3;
+    static unsigned zeros[8192 * 4];
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_cs_walk), zeros, sizeof(zeros)) == hipSuccess ? 0 : -4;
 }
 #endif

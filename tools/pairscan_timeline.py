@@ -4,11 +4,18 @@ launches them (queries produced by fc4 inside the scan, per-point minima combine
 with -DSN_PS_TIMELINE=L -DSN_CS_TIMELINE=L, L = 1 (stamps only) or 2 (every stamp first waits for the memory operations
 before it, i.e. serialised phases):
 
-    library built with those flags (pairscan.hip, geometry_ops.hip);   python tools/pairscan_timeline.py <that library> [B]
+    library built with those flags (pairscan.hip, geometry_ops.hip);   python tools/pairscan_timeline.py <that library> [B] [NET]
 
 Thread 0 of every workgroup stamps the 100 MHz wall clock; printed: median / p10 / p90 over the workgroups of the time
-between consecutive stamps, in microseconds."""
+between consecutive stamps, in microseconds.  In the loss backward lane 0 of EVERY wave also times its ordered owner sum (the
+sum over the points its query owns, operands landed before, result complete after): printed as max / p99 / p90 /
+median / p10 over all waves -- the kernel lasts as long as its slowest wave, and thread 0's median does not see that one.
+
+NET = headline | cls: the queries are what bench.py's network makes of its first batch (the product library runs the forward;
+headline: K = 8, input seed 1234; cls: config1_classification, BatchNorm on the head's output, K = 7, input seed 21) instead of
+a random head on random features -- how many points a query owns, and so how long the slowest wave sums, depends on them."""
 import ctypes
+import os
 import sys
 
 import numpy as np
@@ -16,7 +23,9 @@ import torch
 
 lib = ctypes.CDLL(sys.argv[1])
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
-N, M, K, KF = 1024, 64, 8, 256
+NET = sys.argv[3] if len(sys.argv) > 3 else None
+N, M, K, KF = 1024, 64, 7 if NET == "cls" else 8, 256
+MIN_SIGMA = 0.0 if NET == "cls" else 1e-2
 vp = ctypes.c_void_p
 
 
@@ -32,6 +41,23 @@ scale, shift = torch.ones(KF, device=dev), torch.zeros(KF, device=dev)
 W = torch.randn(3 * M, KF, device=dev, generator=g) * 0.02
 bias = torch.zeros(3 * M, device=dev)
 Q = torch.empty(B, 3, M, device=dev)
+if NET:
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from samplenet_amd import SampleNet
+
+    torch.manual_seed(0)
+    if NET == "cls":
+        net = SampleNet(M, 128, group_size=K, input_shape="bnc", output_shape="bnc", last_fc_batchnorm=True, min_sigma=0.0)
+    else:
+        net = SampleNet(M, 128, group_size=K, initial_temperature=1.0, is_temperature_trainable=True, min_sigma=1e-2,
+                        input_shape="bnc", output_shape="bnc")
+    x = torch.rand(B, N, 3, device=dev, generator=torch.Generator(device=dev).manual_seed(21 if NET == "cls" else 1234)) - 0.5
+    with torch.no_grad():
+        simp, _ = net.to(dev).train()(x)
+    Q.copy_(simp.transpose(1, 2))
+    owned = torch.stack([torch.bincount(r, minlength=M) for r in torch.cdist(x, simp).argmin(2)])
+    print("%s: points owned by a query: mean %.1f, busiest of a cloud %.1f on average, %d at most; %.1f of %d queries own none" %
+          (NET, owned.float().mean(), owned.max(1).values.float().mean(), owned.max(), (owned == 0).sum(1).float().mean(), M))
 idx = torch.empty(B, M, K, device=dev, dtype=torch.int32)
 dq, iq = torch.empty(B, M, device=dev), torch.empty(B, M, device=dev, dtype=torch.int32)
 proj = torch.empty(B, M, 3, device=dev)
@@ -47,8 +73,9 @@ nblocks = B * G
 
 def launch():
     keys.zero_()
-    rc = lib.sn_pairscan_forward_keys(B, N, M, K, P(x), 0, P(Q), P(z3), P(scale), P(shift), P(W), P(bias), KF, P(idx), P(dq), P(iq),
-                                      P(proj), 0, P(T), ctypes.c_float(1e-2), P(keys), P(qpart), P(qmax), st)
+    head = (None, None, None, None, None, 0) if NET else (P(z3), P(scale), P(shift), P(W), P(bias), KF)  # NET: the queries are given
+    rc = lib.sn_pairscan_forward_keys(B, N, M, K, P(x), 0, P(Q), *head, P(idx), P(dq), P(iq),
+                                      P(proj), 0, P(T), ctypes.c_float(MIN_SIGMA), P(keys), P(qpart), P(qmax), st)
     assert rc == 0, rc
 
 
@@ -82,7 +109,7 @@ if hasattr(lib, "sn_debug_chamfer_soft_bwd_timeline"):
 
     def bwd():
         launch()
-        rc = lib.sn_sampler_step_loss_keys(B, N, M, K, P(x), 0, P(Q), P(idx), P(iq), P(keys), P(qpart), P(qmax), G, P(T), cf(1e-2),
+        rc = lib.sn_sampler_step_loss_keys(B, N, M, K, P(x), 0, P(Q), P(idx), P(iq), P(keys), P(qpart), P(qmax), G, P(T), cf(MIN_SIGMA),
                                            cf(0.01), cf(0.01), cf(1.0), P(gl), P(gQ), P(gsig), P(gT), P(dps), P(loss), st, None, None, None)
         assert rc == 0, rc
 
@@ -110,3 +137,9 @@ if hasattr(lib, "sn_debug_chamfer_soft_bwd_timeline"):
         d = t[:, s_] - t[:, s_ - 1]
         print("  %-32s +%.2f  (p10 %.2f  p90 %.2f)   at %.2f" % (names[s_], np.median(d), np.percentile(d, 10), np.percentile(d, 90),
                                                                 np.median(t[:, s_] - t0)))
+    if hasattr(lib, "sn_debug_chamfer_soft_bwd_walk"):
+        w = np.zeros((nb, 4), dtype=np.uint32)
+        assert lib.sn_debug_chamfer_soft_bwd_walk(w.ctypes.data_as(vp), nb) == 0
+        d = (w[w > 0].astype(np.float64) - 1.0) / 100.0
+        print("  ordered owner sum, every wave (%d): max %.2f  p99 %.2f  p90 %.2f  median %.2f  p10 %.2f" %
+              ((d.size, d.max()) + tuple(np.percentile(d, q) for q in (99, 90, 50, 10))))
