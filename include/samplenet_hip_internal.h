@@ -421,6 +421,39 @@ int sn_pose_error_backward(int B, const float *est, const float *gt, const float
                            const float *g_trans_err, float *g_est, sn_stream_t stream);
 int sn_chamfer_mean_per_cloud(int B, int n1, int n2, const float *dist1, const float *dist2, float *out, sn_stream_t stream);
 
+/* The classification task's loss and prediction terms (classification/models/pointnet_cls.py:117-122 get_loss:
+ * tf.nn.sparse_softmax_cross_entropy_with_logits + tf.reduce_mean; classification/evaluate_samplenet.py:237-262: np.argmax of the
+ * logits, `correct`, the per-item loss), ONE launch per direction (csrc/cls_terms.hip).  (They replace a reference interface; they
+ * are declared here because the public header is held at its entry count.)  logits (B,C) fp32, labels (B,) int32.
+ *   ce[b]      = (logf(sum_c expf(x_c - m)) + m) - x_label, m = max_c x_c.
+ *   pred[b]    = numpy's argmax: the FIRST maximum (ties to the lowest class); if a logit is NaN, the index of the first NaN.
+ *   correct[b] = (pred[b] == labels[b]).
+ *   means (2)  = the batch means of ce and of correct.
+ * Mapping and summation order: one wave per row, lane l takes the classes l, l + 64, ... ascending (its partial sum starts at 0),
+ * the 64 lanes combine by the xor butterfly (offsets 32, 16, .. 1); 16 waves per workgroup, wave w takes rows w, w + 16, ...; with
+ * `means` the forward is ONE workgroup: a wave adds its rows' ce ascending from 0, thread 0 adds the 16 wave sums ascending from 0,
+ * one division by (float)B; `correct` is counted in integers (exact) and divided once.  No float atomics: two runs are bit-identical.
+ * Edge cases: a label outside [0, C) gives ce = NaN and correct = 0 and never reads outside logits; a NaN logit gives ce = NaN; a
+ * label whose logit is -inf gives ce = +inf; a row of all -inf gives ce = NaN (pred 0); C = 1 gives ce = 0 exactly; B = 0 is a no-op.
+ * Any B >= 1 and any C >= 1 are served (no refused range).  Every output may be NULL.
+ * _backward (classification/train_samplenet.py:194-199 differentiates get_loss): g_logits (B,C), OVERWRITTEN,
+ *   g_logits[b][c] = (g_means[0] / B + g_ce[b]) * (softmax(x_b)_c - [c == label_b]),
+ * the softmax recomputed from the logits (nothing is saved by the forward).  g_means: DEVICE pointer to the upstream of `means`
+ * (2 floats); only g_means[0] is read -- g_means[1] is NOT (accuracy is a metric), so a pointer to the one scalar serves as well;
+ * g_means and g_ce (B,) may each be NULL (the part is left out).  A bad label gives a NaN row. */
+int sn_classification_terms_forward(int B, int C, const float *logits, const int *labels, float *ce, int *pred, int *correct,
+                                    float *means, sn_stream_t stream);
+int sn_classification_terms_backward(int B, int C, const float *logits, const int *labels, const float *g_means, const float *g_ce,
+                                     float *g_logits, sn_stream_t stream);
+/* sn_nn_matching (samplenet_hip.h) with the two products its kernel computed and dropped: out_idx (B,k) int32 = the indices of the
+ * selected points in selection order -- the first occurrences in idx order, then the farthest-point picks: fps_from_given_indices'
+ * idx, reconstruction/src/samplenet_pointnet_ae.py:515-533 -- and n_unique (B,) int32 = the number of distinct values of idx[b, :]
+ * (classification/evaluate_samplenet.py:227-228, samplenet_pointnet_ae.py:544).  out, out_idx, n_unique may each be NULL; with
+ * complete_fps = 0 out_idx is a copy of idx and n_unique is still computed.  Same kernel body, limits (k <= 1024, N <= 8192) and
+ * `out` bits as sn_nn_matching. */
+int sn_nn_matching_indexed(int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps, float *out,
+                           int *out_idx, int *n_unique, sn_stream_t stream);
+
 /* The progressive sampler's nested prefixes (classification/train_samplenet_progressive.py:157-234) as contiguous tensors in ONE launch:
  * src (B, M, C) of 4-byte elements -> dst[j] (B, sizes[j], C) = src[:, :sizes[j], :] (dst: HOST array of nprefix <= 16 device
  * pointers, NULL entries skipped); and the gradient of that in one launch: out (B, M, C) = sum over j of grads[j] zero-padded to

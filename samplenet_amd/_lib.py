@@ -169,6 +169,9 @@ PROTOTYPES = {
     "sn_pose_error_forward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_pose_error_backward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_chamfer_mean_per_cloud": [_i, _i, _i, _vp, _vp, _vp, _vp],
+    "sn_classification_terms_forward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_classification_terms_backward": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_nn_matching_indexed": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "sn_batch_state_bytes": [],
     "sn_batch_assemble": [_i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _i, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp,
                           _vp, _vp, _vp, _vp],

@@ -408,12 +408,20 @@ class PointNetClsBasic(PointNetCls):
     dropouts = (False, True)
 
 
-def classification_loss(logits, labels, end_points, reg_weight=0.001):
+def classification_loss(logits, labels, end_points, reg_weight=0.001, fused=False):
     """pointnet_cls.py:117-132: mean softmax cross-entropy + reg_weight * l2_loss(T T^T - I) of end_points["transform"] (absent for
-    the basic model: cross-entropy alone, pointnet_cls_basic.py:139-146).  labels: (B,) integer class indices on the GPU."""
+    the basic model: cross-entropy alone, pointnet_cls_basic.py:139-146).  labels: (B,) integer class indices on the GPU.
+    fused=True: the cross-entropy is ops.classification_terms' means[0] (through ops.classification_mean_loss, which hands the
+    upstream scalar straight to the backward entry) -- one HIP launch each way (sn_classification_terms_*)
+    instead of torch's log-softmax / NLL kernels; the default stays F.cross_entropy."""
     if not (logits.is_cuda and labels.is_cuda):
         raise RuntimeError("samplenet_amd.classifier runs on the GPU only; no CPU fallback exists")
-    loss = F.cross_entropy(logits, labels.long())
+    if fused:
+        from . import ops
+
+        loss = ops.classification_mean_loss(logits, labels)  # (= ops.classification_terms(logits, labels)[3][0])
+    else:
+        loss = F.cross_entropy(logits, labels.long())
     t = end_points.get("transform")
     if t is not None:
         loss = loss + reg_weight * orthogonality_loss(t)

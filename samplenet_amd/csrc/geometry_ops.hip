@@ -2266,7 +2266,8 @@ extern "C" int sn_qrot_backward(int B, int N, const float *quat, const float *v,
 template <int PPT>
 __global__ void __launch_bounds__(1024) nn_matching_kernel(int N, int K, int layout, int complete_fps,
                                                            const float *__restrict__ xyz, const int *__restrict__ idx,
-                                                           float *__restrict__ out)
+                                                           float *__restrict__ out, int *__restrict__ out_idx,
+                                                           int *__restrict__ n_unique)
 {
     constexpr int NT = 1024;
     __shared__ int s_sel[1024];      // selected point indices, first-occurrence order then FPS picks (K <= 1024)
@@ -2277,15 +2278,19 @@ __global__ void __launch_bounds__(1024) nn_matching_kernel(int N, int K, int lay
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const float *P = xyz + (size_t)b * 3 * N;
     const int *id = idx + (size_t)b * K;
-    float *o = out + (size_t)b * K * 3;
+    float *o = out ? out + (size_t)b * K * 3 : nullptr;  // (out / out_idx / n_unique: each optional -- sn_nn_matching_indexed)
+    int *oi = out_idx ? out_idx + (size_t)b * K : nullptr;
 
     if (!complete_fps) {
         for (int j = t; j < K; j += NT) {
             const int p = id[j];
+            if (oi) oi[j] = p;
+            if (o) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) o[j * 3 + c] = P[pt_off(layout, N, p, c)];
+                for (int c = 0; c < 3; ++c) o[j * 3 + c] = P[pt_off(layout, N, p, c)];
+            }
         }
-        return;
+        if (!n_unique) return;  // (the distinct count below is still wanted: block-uniform)
     }
     // ---- unique, first-occurrence order
     for (int j = t; j < K; j += NT) {
@@ -2300,7 +2305,9 @@ __global__ void __launch_bounds__(1024) nn_matching_kernel(int N, int K, int lay
         for (int j = 0; j < K; ++j)
             if (s_first[j]) s_sel[n++] = id[j];
         s_t = n;
+        if (n_unique) n_unique[b] = n;  // distinct values of idx[b, :] (evaluate_samplenet.py:227-228)
     }
+    if (!complete_fps) return;
     __syncthreads();
     const int nseed = s_t;
     // ---- this thread's points and their distance to the seed set
@@ -2362,29 +2369,50 @@ __global__ void __launch_bounds__(1024) nn_matching_kernel(int N, int K, int lay
     __syncthreads();
     for (int j = t; j < K; j += NT) {
         const int p = s_sel[j];
+        if (oi) oi[j] = p;
+        if (o) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[j * 3 + c] = P[pt_off(layout, N, p, c)];
+            for (int c = 0; c < 3; ++c) o[j * 3 + c] = P[pt_off(layout, N, p, c)];
+        }
     }
 }
 
 // xyz: (B,N,3) for SN_LAYOUT_BNC or (B,3,N) for SN_LAYOUT_BCN; idx (B,k) int32 in [0,N); out (B,k,3) fp32.
+// One body for both entries: out_idx (B,k) = the selected point indices in selection order, n_unique (B,) = the number of distinct
+// values of idx[b, :]; out, out_idx, n_unique may each be NULL here (sn_nn_matching passes out alone).
+static int nn_matching_launch(const char *who, int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps,
+                              float *out, int *out_idx, int *n_unique, sn_stream_t stream)
+{
+    SN_REQUIRE_AS(who, layout == SN_LAYOUT_BNC || layout == SN_LAYOUT_BCN, "bad layout");
+    if (k > 1024 || N > 8192) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: k <= 1024 and N <= 8192", who);
+    hipStream_t st = (hipStream_t)stream;
+#define SN_NM(PPT_) hipLaunchKernelGGL(nn_matching_kernel<PPT_>, dim3(B), dim3(1024), 0, st, N, k, layout, complete_fps, xyz, idx, out, \
+                                       out_idx, n_unique)
+    if (N <= 1024) SN_NM(1);
+    else if (N <= 2048) SN_NM(2);
+    else if (N <= 4096) SN_NM(4);
+    else SN_NM(8);
+#undef SN_NM
+    SN_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
 extern "C" int sn_nn_matching(int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps, float *out,
                               sn_stream_t stream)
 {
     SN_REQUIRE(B >= 0 && N >= 1 && k >= 1, "bad size");
     if (B == 0) return 0;
     SN_REQUIRE(xyz && idx && out, "null pointer");
-    SN_REQUIRE(layout == SN_LAYOUT_BNC || layout == SN_LAYOUT_BCN, "bad layout");
-    if (k > 1024 || N > 8192) return sn_set_error(SN_ERR_UNSUPPORTED, "sn_nn_matching: k <= 1024 and N <= 8192");
-    hipStream_t st = (hipStream_t)stream;
-#define SN_NM(PPT_) hipLaunchKernelGGL(nn_matching_kernel<PPT_>, dim3(B), dim3(1024), 0, st, N, k, layout, complete_fps, xyz, idx, out)
-    if (N <= 1024) SN_NM(1);
-    else if (N <= 2048) SN_NM(2);
-    else if (N <= 4096) SN_NM(4);
-    else SN_NM(8);
-#undef SN_NM
-    SN_LAUNCH_CHECK();
-    return 0;
+    return nn_matching_launch("sn_nn_matching", B, N, k, xyz, layout, idx, complete_fps, out, nullptr, nullptr, stream);
+}
+
+extern "C" int sn_nn_matching_indexed(int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps, float *out,
+                                      int *out_idx, int *n_unique, sn_stream_t stream)
+{
+    SN_REQUIRE(B >= 0 && N >= 1 && k >= 1, "bad size");
+    if (B == 0 || !(out || out_idx || n_unique)) return 0;
+    SN_REQUIRE(xyz && idx, "null pointer");
+    return nn_matching_launch("sn_nn_matching_indexed", B, N, k, xyz, layout, idx, complete_fps, out, out_idx, n_unique, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -333,6 +333,27 @@ def nn_matching(xyz, idx, k, complete_fps=True, layout=BNC):
     return out
 
 
+def nn_matching_indexed(xyz, idx, k, complete_fps=True, layout=BNC):
+    """nn_matching with the indices it selected: -> (points (B,k,3) float32, out_idx (B,k) int32, n_unique (B,) int32).
+    out_idx: the first occurrences of idx in order, then the farthest-point picks (fps_from_given_indices' idx,
+    samplenet_pointnet_ae.py:515-533; idx itself with complete_fps=False); n_unique: the distinct values of idx[b, :]
+    (evaluate_samplenet.py:227-228).  points is bit-identical to nn_matching's and equals xyz[out_idx].  One launch."""
+    _need_gpu(xyz, idx)
+    xyz = _f32c(xyz.detach())
+    idx = idx.detach().reshape(idx.shape[0], -1).contiguous().int()
+    B = xyz.shape[0]
+    N = xyz.shape[1] if layout == BNC else xyz.shape[2]
+    if idx.shape[1] != k:
+        raise ValueError("nn_matching_indexed: idx must hold k indices per cloud")
+    out = torch.empty(B, k, 3, device=xyz.device, dtype=torch.float32)
+    out_idx = torch.empty(B, k, device=xyz.device, dtype=torch.int32)
+    n_unique = torch.empty(B, device=xyz.device, dtype=torch.int32)
+    with torch.cuda.device(xyz.device):
+        check(lib.sn_nn_matching_indexed(B, N, k, ptr(xyz), layout, ptr(idx), 1 if complete_fps else 0, ptr(out), ptr(out_idx),
+                                         ptr(n_unique), _stream(xyz)), "sn_nn_matching_indexed")
+    return out, out_idx, n_unique
+
+
 def furthest_point_sample(xyz, npoint, layout=BNC):
     """Farthest-point sampling (no gradient): xyz (B,N,3) [BNC] or (B,3,N) [BCN] -> idx (B,npoint) int32.
 
@@ -1106,3 +1127,90 @@ def chamfer_mean_per_cloud(xyz1, xyz2):
             check(lib.sn_chamfer_mean_per_cloud(B, n1, dist2.shape[1], ptr(dist1), ptr(dist2), ptr(out), _stream(dist1)),
                   "sn_chamfer_mean_per_cloud")
     return out
+
+
+# --------------------------------------------------------------------------------------------- classification terms
+class ClassificationTermsFunction(torch.autograd.Function):
+    """logits (B,C), labels (B,) -> ce (B,), pred (B,) int32, correct (B,) int32, means (2,) = the batch means of ce and correct
+    (pointnet_cls.py:117-122, evaluate_samplenet.py:237-262) -- sn_classification_terms_forward / _backward, one launch each way.
+    Gradients flow to the logits through ce and means[0]; means[1] (accuracy) is a metric: its upstream component is not read."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        _need_gpu(logits, labels)
+        logits = _f32c(logits)
+        if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+            raise ValueError("classification_terms: logits (B,C) and labels (B,), got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+        labels = labels.contiguous().int()
+        B, C = logits.shape
+        ce = torch.empty(B, device=logits.device, dtype=torch.float32)
+        pred = torch.empty(B, device=logits.device, dtype=torch.int32)
+        correct = torch.empty(B, device=logits.device, dtype=torch.int32)
+        means = torch.empty(2, device=logits.device, dtype=torch.float32)
+        with torch.cuda.device(logits.device):
+            check(lib.sn_classification_terms_forward(B, C, ptr(logits), ptr(labels), ptr(ce), ptr(pred), ptr(correct), ptr(means),
+                                                      _stream(logits)), "sn_classification_terms_forward")
+        ctx.save_for_backward(logits, labels)
+        ctx.mark_non_differentiable(pred, correct)
+        ctx.set_materialize_grads(False)
+        return ce, pred, correct, means
+
+    @staticmethod
+    def backward(ctx, g_ce, _g_pred, _g_correct, g_means):
+        logits, labels = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        if g_ce is None and g_means is None:
+            return torch.zeros_like(logits), None
+        c = lambda g: None if g is None else g.contiguous().float()  # noqa: E731
+        g_ce, g_means = c(g_ce), c(g_means)
+        g_logits = torch.empty_like(logits)
+        with torch.cuda.device(logits.device):
+            check(lib.sn_classification_terms_backward(logits.shape[0], logits.shape[1], ptr(logits), ptr(labels), ptr(g_means),
+                                                       ptr(g_ce), ptr(g_logits), _stream(logits)), "sn_classification_terms_backward")
+        return g_logits, None
+
+
+def classification_terms(logits, labels):
+    """-> (ce (B,), pred (B,) int32, correct (B,) int32, means (2,)): the per-item softmax cross-entropy, numpy's argmax of the
+    logits, pred == label, and the batch means (loss, accuracy); differentiable in ce and means[0] with respect to the logits."""
+    return ClassificationTermsFunction.apply(logits, labels.detach())
+
+
+class ClassificationMeanLossFunction(torch.autograd.Function):
+    """logits (B,C), labels (B,) -> the batch mean of the softmax cross-entropy as a 0-d tensor (pointnet_cls.py:117-122): means[0] of
+    sn_classification_terms_forward with no per-item output, and sn_classification_terms_backward with the upstream SCALAR itself as
+    g_means (the entry reads g_means[0] only) -- one launch each way, nothing in between (selecting means[0] of classification_terms
+    costs a zero-fill and a copy in the backward)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        _need_gpu(logits, labels)
+        logits = _f32c(logits)
+        if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+            raise ValueError("classification_mean_loss: logits (B,C) and labels (B,), got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+        labels = labels.contiguous().int()
+        means = torch.empty(2, device=logits.device, dtype=torch.float32)
+        with torch.cuda.device(logits.device):
+            check(lib.sn_classification_terms_forward(logits.shape[0], logits.shape[1], ptr(logits), ptr(labels), None, None, None,
+                                                      ptr(means), _stream(logits)), "sn_classification_terms_forward")
+        ctx.save_for_backward(logits, labels)
+        return means[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        g = g.contiguous().float()
+        g_logits = torch.empty_like(logits)
+        with torch.cuda.device(logits.device):
+            check(lib.sn_classification_terms_backward(logits.shape[0], logits.shape[1], ptr(logits), ptr(labels), ptr(g), None,
+                                                       ptr(g_logits), _stream(logits)), "sn_classification_terms_backward")
+        return g_logits, None
+
+
+def classification_mean_loss(logits, labels):
+    """classification_terms' means[0] alone, as a 0-d tensor differentiable in the logits: what classification_loss(fused=True) adds
+    its regulariser to."""
+    return ClassificationMeanLossFunction.apply(logits, labels.detach())

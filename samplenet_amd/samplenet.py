@@ -192,6 +192,45 @@ class SampleNet(nn.Module):
             match = torch.as_tensor(picked, dtype=torch.float32).to(x_bcn.device)
         return (match if out_is_bnc else match.permute(0, 2, 1)).contiguous()  # match is (B,M,3)
 
+    def sample_indices(self, x):
+        """The eval branch's matching WITH its indices, whatever the module's mode (which is left as found), without gradient:
+        x in `input_shape` -> (simplified, matched) in `output_shape` as forward's eval branch, out_idx (B,M) int32 = the matched
+        points' indices in x in selection order (fps_from_given_indices' idx, samplenet_pointnet_ae.py:515-533) and n_unique (B,)
+        int32 = the distinct nearest neighbours before completion (evaluate_samplenet.py:227-228)."""
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                cloud_is_bnc = self.input_shape == "bnc"
+                out_is_bnc = self.output_shape == "bnc"
+                x_bcn = x.permute(0, 2, 1) if cloud_is_bnc else x
+                if x_bcn.shape[1] != 3:
+                    raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
+                y = self._features(x_bcn, x if cloud_is_bnc else None)  # (B,3,M)
+                simp = (y.permute(0, 2, 1) if out_is_bnc else y).contiguous()
+                M = self.num_out_points
+                idx, _ = ops.knn(1, x_bcn.contiguous(), y.contiguous(), ops.BCN, ops.BCN, return_dist=False)  # (B,M,1)
+                if self.device_matching and M <= 1024 and x_bcn.shape[2] <= 8192:
+                    match, out_idx, n_unique = ops.nn_matching_indexed(x_bcn.contiguous(), idx, M, self.complete_fps, ops.BCN)
+                else:  # host round trip through numpy, as _match_inference
+                    pts = x_bcn.permute(0, 2, 1).detach().cpu().numpy()
+                    nn = idx.squeeze(2).cpu().numpy()
+                    picked, sel = sputils.nn_matching(pts, nn, M, complete_fps=self.complete_fps), []
+                    for b in range(pts.shape[0]):  # the picked rows' indices: first match of every picked point, taken once
+                        if not self.complete_fps:
+                            sel.append(nn[b])
+                            continue
+                        first = nn[b][np.sort(np.unique(nn[b], return_index=True)[1])]
+                        rest = [int(np.flatnonzero((pts[b] == p).all(1))[0]) for p in picked[b][len(first):]]
+                        sel.append(np.concatenate([first, np.asarray(rest, dtype=first.dtype)]))
+                    match = torch.as_tensor(picked, dtype=torch.float32).to(x_bcn.device)
+                    out_idx = torch.as_tensor(np.stack(sel).astype(np.int32)).to(x_bcn.device)
+                    n_unique = torch.as_tensor(np.array([len(np.unique(r)) for r in nn], dtype=np.int32)).to(x_bcn.device)
+                match = (match if out_is_bnc else match.permute(0, 2, 1)).contiguous()
+        finally:
+            self.train(was)
+        return simp, match, out_idx, n_unique
+
     def check(self):
         """Host-side health check of the FC chain launches' hand-off state (pointnet.check_chain_errors): raises
         SampleNetHipError when a step since the last check ran on incomplete data (its outputs / gradients were NaN-poisoned on
