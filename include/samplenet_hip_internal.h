@@ -192,13 +192,21 @@ int sn_layer_backward_in3(int R, int Ci, int Co, const float *dy, const float *z
 /* The FC head's BatchNorm + ReLU layers (R <= 32 rows; a0 (R, C0) -> H -> ... -> H, nl layers) as ONE launch: the H / 32
  * workgroups of a layer stay resident and exchange each layer's activations through xbuf with write-through stores and an
  * arrival counter instead of ending the kernel per layer.  Per layer l: W[l] (H, K), bias, BatchNorm parameters / running
- * statistics (training-mode update as sn_layer_forward_bn), outputs z[l] (R, H) pre-BN and coef[l] (4, H).  Bit-identical to
- * nl calls of sn_layer_forward_bn.  xbuf: 2 * 32 * H floats of scratch; sync: 16 WORDS of state spaced 128 bytes apart (16 x 32 unsigned = 2 KB; "sync[i]"
+ * statistics (training-mode update as sn_layer_forward_bn; running_mean[l] set needs running_var[l] set), outputs z[l] (R, H)
+ * pre-BN and coef[l] (4, H).  Against nl calls of sn_layer_forward_bn fed with the same inputs (tests/test_gpu_fc_chain.py; observed
+ * values in profiles/fc_chain/errors.txt): every z[l] and the mean row of coef[l] are bit-identical; scale, invstd within 4 ulps;
+ * shift within 4 ulps of |beta| + |mean scale|; running_mean within 2 and running_var within 8 ulps of the sum of their two terms'
+ * magnitudes (this kernel: fp32 reciprocal square root refined in double, reciprocals from the host, a differently contracted
+ * epilogue).  A row count outside 1..32 is SN_ERR_BAD_ARGUMENT, a width / depth not served SN_ERR_UNSUPPORTED (nl = 4 never fits the
+ * LDS).  xbuf: 2 * 32 * H floats of scratch; sync: 16 WORDS of state spaced 128 bytes apart (16 x 32 unsigned = 2 KB; "sync[i]"
  * below is the 32-bit word at byte offset 128 i: every counter on its own cache line), PERSISTENT and zero-initialised
  * once by the caller (epoch + monotonic arrival counters).  The workgroups of a launch must be RESIDENT TOGETHER (8 x ~137 KB
  * of LDS on otherwise free CUs).  A hand-off poll that gives up -- after sync[13] polls when that word is non-zero, else 2^22 --
  * sets sync[15] and the workgroup writes NaN instead of its outputs; afterwards the counters are out of step: the caller zeroes
- * `sync` before the next launch (samplenet_amd.pointnet.check_chain_errors). */
+ * `sync` before the next launch (samplenet_amd.pointnet.check_chain_errors).  ONE sync block per depth: a launch advances the
+ * counters of the seams IT has (forward: sync[1 .. nl - 1]; backward: sync[1 .. ns - 1] and sync[14]) to 8 (16) times the epoch, so a
+ * block shared between launches of different nl / ns leaves the other depth's counters out of step with sync[0].  The counters wrap
+ * modulo 2^32 by design (the polls compare the signed difference). */
 int sn_fc_chain_forward_supported(int R, int C0, int H, int nl);
 int sn_fc_chain_forward(int R, int C0, int H, int nl, const float *a0, const float *const *W, const float *const *bias,
                         const float *const *gamma, const float *const *beta, float *const *running_mean,
@@ -243,7 +251,10 @@ int sn_fc_chain_forward_pool_out(int B, int N, int nconv, long long *acc, const 
  * stage: dW[s], the layer below's dgamma / dbeta / dbias; db_top: bias gradient of the top layer; aprev[s] / araw[s]: the
  * weight-gradient operand (zprev with ReLU(BN) applied, or a raw input such as the pooled features).  Last stage also
  * returns gout (R, Ci) = the masked gradient and kout (3, Ci) = the dZ coefficients of the BatchNorm below (what
- * sn_conv_stack_backward takes as gsel / kcoef_top).  gy: (R, Co[0]).  Bit-identical to the sn_layer_backward chain.
+ * sn_conv_stack_backward takes as gsel / kcoef_top).  gy: (R, Co[0]).  db_top, any dbias[s], gout and kout may be NULL (the other
+ * outputs do not change by a bit).  Same arithmetic as the sn_layer_backward chain up to the contraction of the epilogues (the module
+ * tests hold the two to 2e-5 / 6e-5); against fp64 every output stays under the first-order bounds counted in tests/fc_chain_ref.py,
+ * and integer data comes out bit-exact.  One sync block per depth ns (see sn_fc_chain_forward).
  * xbuf: ns * 32 * 256 floats of scratch; sync: 16 x 32 unsigned (same layout) of its OWN persistent zero-initialised state (launch epoch, one
  * monotonic arrival counter per stage, epoch-reader count; sync[13] / sync[15] and the NaN poisoning as sn_fc_chain_forward;
  * 16 workgroups must be resident together). */
@@ -256,7 +267,8 @@ int sn_fc_chain_backward(int R, int ns, const int *Co, const int *Ci, const floa
 /* sn_fc_chain_backward for a head whose output went through a BatchNorm WITHOUT activation (the classification sampler's output
  * layer: sn_layer_forward_bn_out / sn_fc_chain_forward_pool_out): gy is the gradient behind that BatchNorm, zo (R, Co[0]) its
  * input, coef_o (4, Co[0]) the forward's coefficients; the launch opens with that BatchNorm's backward (the arithmetic of
- * sn_bn_output_backward, rows summed in order) and leaves dgamma_o / dbeta_o (Co[0]).  fixed != 0: running statistics. */
+ * sn_bn_output_backward, rows summed in order) and leaves dgamma_o / dbeta_o (Co[0]).  fixed != 0: running statistics.
+ * Bit-identical, every output, to sn_bn_output_backward followed by sn_fc_chain_backward on its dz. */
 int sn_fc_chain_backward_obn(int R, int ns, const int *Co, const int *Ci, const float *gy, const float *zo, const float *coef_o, int fixed,
                              float *dgamma_o, float *dbeta_o, const float *const *W, const float *const *zprev,
                              const float *const *coefprev, const long long *bn_rows, float *const *dgamma, float *const *dbeta,

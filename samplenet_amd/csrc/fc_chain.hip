@@ -1,7 +1,8 @@
 // fc_chain.hip -- the FC head of the sampler (registration/src/samplenet.py:53-59, :97-104: 3 x [Linear -> BatchNorm1d -> ReLU],
 // rows R <= 32) as ONE resident-workgroup launch per direction: the workgroups of a layer keep running and hand activations /
 // gradients to each other through write-through stores and arrival counters instead of ending the kernel after every layer.
-// Arithmetic is that of the layer-by-layer R <= 32 kernels in pointnet_mlp.hip (bit-identical results).
+// The GEMM arithmetic is that of the layer-by-layer R <= 32 kernels in pointnet_mlp.hip (pre-BatchNorm outputs bit-identical; the
+// coefficients agree to a few ulps: include/samplenet_hip_internal.h states the figures, tests/test_gpu_fc_chain.py holds them).
 #include "mlp_device.h"
 
 namespace sn {
@@ -19,8 +20,8 @@ namespace sn {
 // exit: observed placement b % 8 -> XCD, a speed matter only).  Arrival counters are monotonic over launches: the epoch word
 // is read by every workgroup before its first arrival and advanced by workgroup 0 after the first seam (no reset, no host
 // involvement: safe under graph replay).  A poll that exceeds its bound sets the error word instead of hanging the GPU.
-// Arithmetic (K split, summation order, BatchNorm expressions) is that of small_fwd_lds_kernel: results are bit-identical
-// to the layer-by-layer launches.
+// Arithmetic (K split, summation order, BatchNorm expressions) is that of small_fwd_lds_kernel: z and the batch mean are bit-identical
+// to the layer-by-layer launches, the other coefficients within a few ulps (reciprocal square root and reciprocals computed differently).
 // ------------------------------------------------------------------------------------------------
 constexpr int kFcChainMaxLayers = 4;
 struct FcChainLayer {
@@ -925,12 +926,15 @@ extern "C" int sn_fc_chain_forward(int R, int C0, int H, int nl, const float *a0
                                    const float *momentum, float *const *z, float *const *coef, float *xbuf, unsigned *sync,
                                    sn_stream_t stream)
 {
-    SN_REQUIRE(sn_fc_chain_forward_supported(R, C0, H, nl), "shape not supported (sn_fc_chain_forward_supported)");
+    SN_REQUIRE(R >= 1 && R <= 32, "1 to 32 rows");
+    if (!sn_fc_chain_forward_supported(R, C0, H, nl))
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: shape not supported (sn_fc_chain_forward_supported)", __func__);
     SN_REQUIRE(a0 && W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
     FcChainArgs g{};
     g.a0 = a0, g.R = R, g.C0 = C0, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
     for (int l = 0; l < nl; ++l) {
         SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
+        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
         g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
                               running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
                               z[l], coef[l], eps[l], momentum[l]};
@@ -976,7 +980,9 @@ extern "C" int sn_fc_chain_forward_pool(int B, int N, int nconv, long long *acc,
                                         sn_stream_t stream)
 {
     constexpr int C0 = 128;
-    SN_REQUIRE(sn_fc_chain_forward_pool_supported(B, N, C0, H, nl) && nconv >= 2, "shape not supported (sn_fc_chain_forward_pool_supported)");
+    SN_REQUIRE(B >= 1 && B <= 32 && N >= 1 && nconv >= 2, "1 to 32 clouds, N >= 1, nconv >= 2");
+    if (!sn_fc_chain_forward_pool_supported(B, N, C0, H, nl))
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: shape not supported (sn_fc_chain_forward_pool_supported)", __func__);
     SN_REQUIRE(acc && pool_val && pool_idx && gamma5 && beta5 && running_mean5 && running_var5 && coef5 && pooled && argsel && zsel,
                "null pointer");
     SN_REQUIRE(W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
@@ -989,6 +995,7 @@ extern "C" int sn_fc_chain_forward_pool(int B, int N, int nconv, long long *acc,
     g.P.pooled = pooled, g.P.argsel = argsel, g.P.zsel = zsel;
     for (int l = 0; l < nl; ++l) {
         SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
+        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
         g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
                               running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
                               z[l], coef[l], eps[l], momentum[l]};
@@ -1022,11 +1029,14 @@ extern "C" int sn_fc_chain_forward_pool_out(int B, int N, int nconv, long long *
                                             float momentum_o, float *zo, float *coef_o, float *y, sn_stream_t stream)
 {
     constexpr int C0 = 128;
-    SN_REQUIRE(sn_fc_chain_forward_pool_out_supported(B, N, C0, H, nl, Co) && nconv >= 2, "shape not supported (sn_fc_chain_forward_pool_out_supported)");
+    SN_REQUIRE(B >= 1 && B <= 32 && N >= 1 && nconv >= 2, "1 to 32 clouds, N >= 1, nconv >= 2");
+    if (!sn_fc_chain_forward_pool_out_supported(B, N, C0, H, nl, Co))
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: shape not supported (sn_fc_chain_forward_pool_out_supported)", __func__);
     SN_REQUIRE(acc && pool_val && pool_idx && gamma5 && beta5 && running_mean5 && running_var5 && coef5 && pooled && argsel && zsel,
                "null pointer");
     SN_REQUIRE(W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
     SN_REQUIRE(Wo && bo && gamma_o && beta_o && zo && coef_o && y, "null output-layer pointer");
+    SN_REQUIRE(!running_mean_o || running_var_o, "running_mean without running_var (output layer)");
     FcChainArgs g{};
     g.a0 = pooled, g.R = B, g.C0 = C0, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
     g.P.acc = acc + (size_t)(nconv - 1) * kFxLayer, g.P.zero_ptr = acc + (size_t)(nconv - 2) * kFxLayer, g.P.zero_n = kFxLayer;
@@ -1036,6 +1046,7 @@ extern "C" int sn_fc_chain_forward_pool_out(int B, int N, int nconv, long long *
     g.P.pooled = pooled, g.P.argsel = argsel, g.P.zsel = zsel;
     for (int l = 0; l < nl; ++l) {
         SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
+        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
         g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
                               running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
                               z[l], coef[l], eps[l], momentum[l]};
@@ -1050,13 +1061,12 @@ extern "C" int sn_fc_chain_forward_pool_out(int B, int N, int nconv, long long *
     return 0;
 }
 
-// (sn_fc_chain_backward_obn hands the output BatchNorm's operands to the launch below: thread-local, consumed by the next call)
+// the output BatchNorm's operands of sn_fc_chain_backward_obn (z == NULL: none)
 struct FcBwdOutBn {
     const float *z, *coef;
     float *dgamma, *dbeta;
     int fixed;
 };
-static thread_local FcBwdOutBn g_obn{};
 
 // 1: sn_fc_chain_backward runs this FC head's backward (ns GEMM layers, top first: Co[s] x Ci[s]) as one launch
 extern "C" int sn_fc_chain_backward_supported(int R, int ns, const int *Co, const int *Ci)
@@ -1070,18 +1080,21 @@ extern "C" int sn_fc_chain_backward_supported(int R, int ns, const int *Co, cons
     return 1;
 }
 
-extern "C" int sn_fc_chain_backward(int R, int ns, const int *Co, const int *Ci, const float *gy, const float *const *W,
-                                    const float *const *zprev, const float *const *coefprev, const long long *bn_rows,
-                                    float *const *dgamma, float *const *dbeta, float *const *dbias, float *const *dW, float *db_top,
-                                    const float *const *aprev, const int *araw, float *gout, float *kout, float *xbuf,
-                                    unsigned *sync, sn_stream_t stream)
+// (both entries: `who` names the one that was called in its refusals)
+static int fc_chain_backward_impl(const char *who, const FcBwdOutBn &obn, int R, int ns, const int *Co, const int *Ci, const float *gy,
+                                  const float *const *W, const float *const *zprev, const float *const *coefprev, const long long *bn_rows,
+                                  float *const *dgamma, float *const *dbeta, float *const *dbias, float *const *dW, float *db_top,
+                                  const float *const *aprev, const int *araw, float *gout, float *kout, float *xbuf, unsigned *sync,
+                                  sn_stream_t stream)
 {
-    SN_REQUIRE(sn_fc_chain_backward_supported(R, ns, Co, Ci), "shape not supported (sn_fc_chain_backward_supported)");
-    SN_REQUIRE(gy && W && zprev && coefprev && bn_rows && dgamma && dbeta && dbias && dW && aprev && araw && xbuf && sync, "null pointer");
+    SN_REQUIRE_AS(who, R >= 1 && R <= 32 && Co && Ci, "1 to 32 rows, Co and Ci given");
+    if (!sn_fc_chain_backward_supported(R, ns, Co, Ci))
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: shape not supported (sn_fc_chain_backward_supported)", who);
+    SN_REQUIRE_AS(who, gy && W && zprev && coefprev && bn_rows && dgamma && dbeta && dbias && dW && aprev && araw && xbuf && sync, "null pointer");
     FcBwdArgs g{};
     g.gy = gy, g.R = R, g.ns = ns, g.xbuf = xbuf, g.sync = sync;
     for (int s = 0; s < ns; ++s) {
-        SN_REQUIRE(W[s] && zprev[s] && coefprev[s] && dgamma[s] && dbeta[s] && dW[s] && aprev[s], "null stage pointer");
+        SN_REQUIRE_AS(who, W[s] && zprev[s] && coefprev[s] && dgamma[s] && dbeta[s] && dW[s] && aprev[s], "null stage pointer");
         FcBwdStage &S = g.S[s];
         S.W = W[s], S.Co = Co[s], S.Ci = Ci[s], S.zprev = zprev[s], S.coefprev = coefprev[s], S.bn_rows = bn_rows[s];
         S.rinv = bn_rows[s] > 0 ? 1.0 / (double)bn_rows[s] : 0.0;
@@ -1089,15 +1102,24 @@ extern "C" int sn_fc_chain_backward(int R, int ns, const int *Co, const int *Ci,
         S.aprev = aprev[s], S.araw = araw[s];
         S.gout = s == ns - 1 ? gout : nullptr, S.kout = s == ns - 1 ? kout : nullptr;
     }
-    if (g_obn.z) g.oz = g_obn.z, g.ocoef = g_obn.coef, g.odgamma = g_obn.dgamma, g.odbeta = g_obn.dbeta, g.ofixed = g_obn.fixed;
-    g_obn = FcBwdOutBn{};
+    if (obn.z) g.oz = obn.z, g.ocoef = obn.coef, g.odgamma = obn.dgamma, g.odbeta = obn.dbeta, g.ofixed = obn.fixed;
     const size_t lds = ((size_t)3 * 32 * 260 + kRsFloats + 32 * 36) * sizeof(float);
     static SnLdsAttr attr;
-    if (sn_lds_attr(attr, (const void *)fc_chain_bwd_kernel, lds, "sn_fc_chain_backward")) return SN_ERR_UNSUPPORTED;
+    if (sn_lds_attr(attr, (const void *)fc_chain_bwd_kernel, lds, who)) return SN_ERR_UNSUPPORTED;
     // 128 blocks: b % 8 == 0 -> XCD 0; b / 8 = 0..7 the chain, 8..15 the weight-gradient workgroups
     hipLaunchKernelGGL(fc_chain_bwd_kernel, dim3(128), dim3(256), lds, (hipStream_t)stream, g);
-    SN_LAUNCH_CHECK();
+    SN_LAUNCH_CHECK_AS(who);
     return 0;
+}
+
+extern "C" int sn_fc_chain_backward(int R, int ns, const int *Co, const int *Ci, const float *gy, const float *const *W,
+                                    const float *const *zprev, const float *const *coefprev, const long long *bn_rows,
+                                    float *const *dgamma, float *const *dbeta, float *const *dbias, float *const *dW, float *db_top,
+                                    const float *const *aprev, const int *araw, float *gout, float *kout, float *xbuf,
+                                    unsigned *sync, sn_stream_t stream)
+{
+    return fc_chain_backward_impl(__func__, FcBwdOutBn{}, R, ns, Co, Ci, gy, W, zprev, coefprev, bn_rows, dgamma, dbeta, dbias, dW, db_top, aprev,
+                                  araw, gout, kout, xbuf, sync, stream);
 }
 
 // sn_fc_chain_backward for a head whose output went through a BatchNorm WITHOUT activation (classification sampler: sn_layer_forward_bn_out
@@ -1111,9 +1133,6 @@ extern "C" int sn_fc_chain_backward_obn(int R, int ns, const int *Co, const int 
                                         float *gout, float *kout, float *xbuf, unsigned *sync, sn_stream_t stream)
 {
     SN_REQUIRE(zo && coef_o && dgamma_o && dbeta_o, "null output-BatchNorm pointer");
-    g_obn = FcBwdOutBn{zo, coef_o, dgamma_o, dbeta_o, fixed ? 1 : 0};
-    const int rc = sn_fc_chain_backward(R, ns, Co, Ci, gy, W, zprev, coefprev, bn_rows, dgamma, dbeta, dbias, dW, db_top, aprev, araw, gout,
-                                        kout, xbuf, sync, stream);
-    g_obn = FcBwdOutBn{};
-    return rc;
+    return fc_chain_backward_impl(__func__, FcBwdOutBn{zo, coef_o, dgamma_o, dbeta_o, fixed ? 1 : 0}, R, ns, Co, Ci, gy, W, zprev, coefprev, bn_rows,
+                                  dgamma, dbeta, dbias, dW, db_top, aprev, araw, gout, kout, xbuf, sync, stream);
 }

@@ -5,7 +5,7 @@ any device work.  So do the entries of include/samplenet_hip_internal.h that the
 (sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
 transforms, the orthogonality regulariser and sn_bn_relu_*, and the nine entries of the one-batch task evaluation (cyclic padding, the
 valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped), and the twelve entries of the sampler
-step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 import json
@@ -145,8 +145,36 @@ SKINNY = {
 }
 
 
+# The five FC-chain entries (csrc/fc_chain.hip).  Their per-layer / per-stage operands are HOST arrays of device pointers, eps / momentum
+# host float arrays, Co / Ci / araw host int arrays and bn_rows a host array of long long (spelled as pairs of ints): the bases hold two
+# layers (forward, backward) or the three the pool entries serve, so every case is spelled out in _fc_chain_cases().  A row count outside
+# 1..32 is a BAD argument; a width or depth the kernels do not serve is UNSUPPORTED (callers ask the `_supported` query first).
+_P2, _P3, _F2, _F3 = [HOSTP, 4096, 4096], [HOSTP, 4096, 4096, 4096], [HOSTI, 0, 0], [HOSTI, 0, 0, 0]
+_POOL = [4, 64, 5, Pp, Pp, Pp, Pp, Pp, Pp, Pp, None, 1e-5, 0.1, Pp, Pp, Pp, Pp, 256, 3, _P3, _P3, _P3, _P3, None, None, None, _F3, _F3, _P3, _P3,
+         Pp, Pp]
+_POOL_REQ = [3, 4, 5, 6, 7, 8, 9, 13, 14, 15, 16, 19, 20, 21, 22, 26, 27, 28, 29, 30, 31]
+_BWD = [_P2, _P2, _P2, [HOSTI, 4, 0, 4, 0], _P2, _P2, _P2, _P2, None, _P2, [HOSTI, 0, 0], None, None, Pp, Pp, None]
+FC_CHAIN = {
+    # R, C0, H, nl, a0, W, bias, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, z, coef, xbuf, sync, stream
+    "sn_fc_chain_forward": ([4, 128, 256, 2, Pp, _P2, _P2, _P2, _P2, None, None, None, _F2, _F2, _P2, _P2, Pp, Pp, None],
+                            [4, 5, 6, 7, 8, 12, 13, 14, 15, 16, 17], [5, 6, 7, 8, 14, 15]),
+    # B, N, nconv, acc, pool_val, pool_idx, gamma5, beta5, running_mean5, running_var5, num_batches_tracked5, eps5, momentum5, coef5, pooled,
+    # argsel, zsel, H, nl, W, bias, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, z, coef, xbuf, sync, stream
+    "sn_fc_chain_forward_pool": (_POOL + [None], _POOL_REQ, [19, 20, 21, 22, 28, 29]),
+    # ... sync, Co, Wo, bo, gamma_o, beta_o, running_mean_o, running_var_o, num_batches_tracked_o, eps_o, momentum_o, zo, coef_o, y, stream
+    "sn_fc_chain_forward_pool_out": (_POOL + [96, Pp, Pp, Pp, Pp, None, None, None, 1e-5, 0.1, Pp, Pp, Pp, None],
+                                     _POOL_REQ + [33, 34, 35, 36, 42, 43, 44], [19, 20, 21, 22, 28, 29]),
+    # R, ns, Co, Ci, gy, W, zprev, coefprev, bn_rows, dgamma, dbeta, dbias, dW, db_top, aprev, araw, gout, kout, xbuf, sync, stream
+    "sn_fc_chain_backward": ([4, 2, [HOSTI, 256, 256], [HOSTI, 256, 128], Pp] + _BWD, [2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 18, 19],
+                             [5, 6, 7, 9, 10, 12, 14]),
+    # R, ns, Co, Ci, gy, zo, coef_o, fixed, dgamma_o, dbeta_o, W, zprev, ... as above
+    "sn_fc_chain_backward_obn": ([4, 2, [HOSTI, 256, 256], [HOSTI, 256, 128], Pp, Pp, Pp, 0, Pp, Pp] + _BWD,
+                                 [2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 19, 20, 23, 24], [10, 11, 12, 14, 15, 17, 19]),
+}
+
+
 def _with(name, changes):
-    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY[name])[0])
+    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY.get(name) or FC_CHAIN[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -210,7 +238,7 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
-    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases()
+    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases() + _fc_chain_cases()
 
 
 def _skinny_cases():
@@ -317,6 +345,43 @@ def _step_loss_cases():
     return out
 
 
+def _fc_chain_cases():
+    out = []
+    add = lambda cid, name, ch, text=None, code=BAD: out.append(("%s-%s" % (name, cid), name, _with(name, ch), code, text or name))
+    for name, (base, required, arrays) in FC_CHAIN.items():
+        for pos in required:
+            add("arg%d-null" % pos, name, {pos: None})
+        for pos in arrays:  # a NULL inside a per-layer / per-stage host array, in its last place
+            add("arg%d-holds-a-null" % pos, name, {pos: base[pos][:-1] + [0]}, "null layer pointer" if "forward" in name else "null stage pointer")
+        for r in (0, -1, 33):
+            add("rows-%d" % r, name, {0: r})
+    fw, fp, fo, bw, bo = FC_CHAIN
+    for cid, ch in (("C0-96", {1: 96}), ("C0-512", {1: 512}), ("H-128", {2: 128}), ("nl-1", {3: 1}), ("nl-5", {3: 5}),
+                    ("nl-4-needs-too-much-LDS", {3: 4})):
+        add(cid, fw, ch, "shape not supported", UNSUP)
+    for name in (fp, fo):
+        for cid, ch in (("N-32", {1: 32}), ("N-96", {1: 96}), ("H-128", {17: 128}), ("nl-2", {18: 2})):
+            add(cid, name, ch, "shape not supported", UNSUP)
+        add("N-negative", name, {1: -1})
+        add("nconv-1", name, {2: 1})
+    for co in (0, 16, 48, 288):
+        add("Co-%d" % co, fo, {32: co}, "shape not supported", UNSUP)
+    # running_mean[l] given while running_var[l] is NULL: the kernel would read through the NULL
+    for name, (rm, rv) in ((fw, (9, 10)), (fp, (23, 24)), (fo, (23, 24))):
+        n = len(FC_CHAIN[name][0][rm - 4]) - 1  # (the W array sits four places in front: as many layers)
+        full, last_null, only_last = [HOSTP] + [4096] * n, [HOSTP] + [4096] * (n - 1) + [0], [HOSTP] + [0] * (n - 1) + [4096]
+        add("running_mean-without-the-running_var-array", name, {rm: full}, "running_mean without running_var")
+        add("running_mean-with-a-null-running_var", name, {rm: full, rv: last_null}, "running_mean without running_var")
+        add("the-last-running_mean-alone", name, {rm: only_last, rv: last_null}, "running_mean without running_var")
+    add("running_mean_o-without-running_var_o", fo, {37: Pp}, "running_mean without running_var")
+    for name in (bw, bo):
+        for cid, ch in (("Co-96", {2: [HOSTI, 96, 256]}), ("Co-320", {2: [HOSTI, 320, 256]}), ("Ci-48", {3: [HOSTI, 256, 48]}),
+                        ("Ci-288", {3: [HOSTI, 256, 288]}), ("inner-Ci-128", {2: [HOSTI, 256, 128], 3: [HOSTI, 128, 128]}),
+                        ("Co-is-not-the-Ci-above", {2: [HOSTI, 256, 128]}), ("ns-1", {1: 1}), ("ns-6", {1: 6}), ("ns-negative", {1: -1})):
+            add(cid, name, ch, "shape not supported", UNSUP)
+    return out
+
+
 def _transform_cases(nulled):
     out = []
     tf, tb, of, ob = "sn_cloud_transform_forward", "sn_cloud_transform_backward", "sn_orthogonality_loss_forward", "sn_orthogonality_loss_backward"
@@ -343,7 +408,7 @@ def _transform_cases(nulled):
 
 
 CASES = _cases()
-IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
+IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + sorted(FC_CHAIN) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
                                                "sn_skinny_linear_scratch_bytes"]
 
 _CHILD = r"""
@@ -398,6 +463,14 @@ def test_the_table_walks_every_entry_in_scope():
         for pos, ty in enumerate(proto):
             assert (ty is ctypes.c_void_p) == (base[pos] in (Pp, None)), (name, pos)
             assert pos not in required or base[pos] == Pp, (name, pos)
+    for name, (base, required, arrays) in FC_CHAIN.items():
+        proto = _lib.PROTOTYPES[name]
+        assert len(base) == len(proto) and set(arrays) <= set(required), name
+        for pos, ty in enumerate(proto):
+            is_ptr = base[pos] is None or base[pos] == Pp or isinstance(base[pos], list)
+            assert (ty is ctypes.c_void_p) == is_ptr, (name, pos)
+            assert pos not in required or base[pos] is not None, (name, pos)
+            assert pos not in arrays or base[pos][0] == HOSTP, (name, pos)
     assert not [n for n in IN_SCOPE if n not in _lib.PROTOTYPES]
     assert len({c[0] for c in CASES}) == len(CASES)
 
