@@ -1432,85 +1432,6 @@ extern "C" int sn_sigma_grad(int nparts, const float *partial, const float *temp
     return 0;
 }
 
-extern "C" int sn_soft_project_backward(int b, int n, int m, int k, const float *P, int p_layout, const float *Q,
-                                        int q_layout, const int *idx, const float *temperature, float min_sigma,
-                                        const float *grad_proj, int gproj_layout, float *grad_Q, int gq_layout,
-                                        float *grad_P, float *grad_sigma_partial, sn_stream_t stream)
-{
-    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE((p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN) && (q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN),
-               "bad p_layout / q_layout");
-    SN_REQUIRE((gproj_layout == SN_LAYOUT_BNC || gproj_layout == SN_LAYOUT_BCN) && (gq_layout == SN_LAYOUT_BNC || gq_layout == SN_LAYOUT_BCN),
-               "bad gproj_layout / gq_layout");
-    SN_REQUIRE(P && Q && idx && temperature && grad_proj, "null input");
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = p_layout, a.q_layout = q_layout, a.n = n, a.m = m, a.k = k;
-    a.grad_proj = grad_proj, a.gproj_layout = gproj_layout;
-    a.grad_Q = grad_Q, a.gq_layout = gq_layout, a.grad_P = grad_P, a.grad_sigma_partial = grad_sigma_partial;
-    hipLaunchKernelGGL(soft_bwd_kernel<true>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    SN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sn_soft_weights_forward(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
-                                       const float *temperature, float min_sigma, float *weights,
-                                       sn_stream_t stream)
-{
-    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE(P && Q && idx && temperature && weights, "null pointer");
-    const int y = std::max(1, std::min((m + 3) / 4, (1024 + b - 1) / b));
-    hipLaunchKernelGGL(soft_weights_fwd_kernel, dim3(b, y), dim3(256), 0, (hipStream_t)stream, n, m, k, P, Q, idx,
-                       temperature, min_sigma, weights);
-    SN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sn_soft_weights_backward(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
-                                        const float *temperature, float min_sigma, const float *weights,
-                                        const float *grad_weights, float *grad_Q, float *grad_P,
-                                        float *grad_sigma_partial, sn_stream_t stream)
-{
-    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE(P && Q && idx && temperature && grad_weights, "null input");
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = SN_LAYOUT_BCN, a.q_layout = SN_LAYOUT_BCN, a.n = n, a.m = m, a.k = k;
-    a.weights_in = weights, a.grad_weights = grad_weights;
-    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.grad_P = grad_P, a.grad_sigma_partial = grad_sigma_partial;
-    hipLaunchKernelGGL(soft_bwd_kernel<false>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    SN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sn_weighted_gather_forward(int b, int c, int n, int m, int k, const float *X, const int *idx,
-                                          const float *weights, float *out, sn_stream_t stream)
-{
-    SN_REQUIRE(b >= 0 && c >= 0 && n >= 1 && m >= 0 && k >= 1, "bad size");
-    if (b == 0 || m == 0 || c == 0) return 0;
-    SN_REQUIRE(X && idx && weights && out, "null pointer");
-    hipLaunchKernelGGL(weighted_gather_fwd_kernel, dim3(((size_t)c * m + 255) / 256, b), dim3(256), 0,
-                       (hipStream_t)stream, c, n, m, k, X, idx, weights, out);
-    SN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sn_weighted_gather_backward(int b, int c, int n, int m, int k, const float *X, const int *idx,
-                                           const float *weights, const float *grad_out, float *grad_weights,
-                                           float *grad_X, sn_stream_t stream)
-{
-    SN_REQUIRE(b >= 0 && c >= 0 && n >= 1 && m >= 0 && k >= 1, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE(X && idx && weights && grad_out, "null pointer");
-    hipLaunchKernelGGL(weighted_gather_bwd_kernel, dim3(((size_t)m * k + 255) / 256, b), dim3(256), 0,
-                       (hipStream_t)stream, c, n, m, k, X, idx, weights, grad_out, grad_weights, grad_X);
-    SN_LAUNCH_CHECK();
-    return 0;
-}
-
 // dst (b, n, c) [or (b, c, n)] = index-add of src over idx (b, ne): ordered and deterministic up to kIndexAddOrderedWork
 // index loads per cloud, float atomics into a zeroed destination beyond
 template <bool CHANNEL_MAJOR>
@@ -1532,6 +1453,120 @@ static int launch_index_add(const char *who, int b, int n, int c, long long ne, 
     return 0;
 }
 
+// The three backward entries below come in pairs: NAME sums the gradient towards the point cloud / the features by unordered
+// float atomics (scratch == NULL here), NAME_ordered (ordered) needs grad_P / grad_X and scratch.
+static int soft_project_backward_impl(const char *who, int b, int n, int m, int k, const float *P, int p_layout, const float *Q,
+                                      int q_layout, const int *idx, const float *temperature, float min_sigma,
+                                      const float *grad_proj, int gproj_layout, float *grad_Q, int gq_layout, float *grad_P,
+                                      float *grad_sigma_partial, float *scratch, bool ordered, sn_stream_t stream)
+{
+    SN_REQUIRE_AS(who, b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
+    if (b == 0 || m == 0) return 0;
+    SN_REQUIRE_AS(who, (p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN) && (q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN),
+                  "bad p_layout / q_layout");
+    SN_REQUIRE_AS(who, (gproj_layout == SN_LAYOUT_BNC || gproj_layout == SN_LAYOUT_BCN) && (gq_layout == SN_LAYOUT_BNC || gq_layout == SN_LAYOUT_BCN),
+                  "bad gproj_layout / gq_layout");
+    SN_REQUIRE_AS(who, P && Q && idx && temperature && grad_proj && (!ordered || (grad_P && scratch)),
+                  ordered ? "null pointer" : "null input");
+    SoftBwdArgs a{};
+    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
+    a.p_layout = p_layout, a.q_layout = q_layout, a.n = n, a.m = m, a.k = k;
+    a.grad_proj = grad_proj, a.gproj_layout = gproj_layout;
+    a.grad_Q = grad_Q, a.gq_layout = gq_layout, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
+    hipLaunchKernelGGL(soft_bwd_kernel<true>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
+    if (ordered)
+        return p_layout == SN_LAYOUT_BNC ? launch_index_add<false>(who, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream)
+                                         : launch_index_add<true>(who, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    SN_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+extern "C" int sn_soft_project_backward(int b, int n, int m, int k, const float *P, int p_layout, const float *Q,
+                                        int q_layout, const int *idx, const float *temperature, float min_sigma,
+                                        const float *grad_proj, int gproj_layout, float *grad_Q, int gq_layout,
+                                        float *grad_P, float *grad_sigma_partial, sn_stream_t stream)
+{
+    return soft_project_backward_impl(__func__, b, n, m, k, P, p_layout, Q, q_layout, idx, temperature, min_sigma, grad_proj,
+                                      gproj_layout, grad_Q, gq_layout, grad_P, grad_sigma_partial, nullptr, false, stream);
+}
+
+extern "C" int sn_soft_weights_forward(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
+                                       const float *temperature, float min_sigma, float *weights,
+                                       sn_stream_t stream)
+{
+    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
+    if (b == 0 || m == 0) return 0;
+    SN_REQUIRE(P && Q && idx && temperature && weights, "null pointer");
+    const int y = std::max(1, std::min((m + 3) / 4, (1024 + b - 1) / b));
+    hipLaunchKernelGGL(soft_weights_fwd_kernel, dim3(b, y), dim3(256), 0, (hipStream_t)stream, n, m, k, P, Q, idx,
+                       temperature, min_sigma, weights);
+    SN_LAUNCH_CHECK();
+    return 0;
+}
+
+static int soft_weights_backward_impl(const char *who, int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
+                                      const float *temperature, float min_sigma, const float *weights, const float *grad_weights,
+                                      float *grad_Q, float *grad_P, float *grad_sigma_partial, float *scratch, bool ordered,
+                                      sn_stream_t stream)
+{
+    SN_REQUIRE_AS(who, b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
+    if (b == 0 || m == 0) return 0;
+    SN_REQUIRE_AS(who, P && Q && idx && temperature && grad_weights && (!ordered || (grad_P && scratch)),
+                  ordered ? "null pointer" : "null input");
+    SoftBwdArgs a{};
+    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
+    a.p_layout = SN_LAYOUT_BCN, a.q_layout = SN_LAYOUT_BCN, a.n = n, a.m = m, a.k = k;
+    a.weights_in = weights, a.grad_weights = grad_weights;
+    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
+    hipLaunchKernelGGL(soft_bwd_kernel<false>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
+    if (ordered) return launch_index_add<true>(who, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    SN_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+extern "C" int sn_soft_weights_backward(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
+                                        const float *temperature, float min_sigma, const float *weights,
+                                        const float *grad_weights, float *grad_Q, float *grad_P,
+                                        float *grad_sigma_partial, sn_stream_t stream)
+{
+    return soft_weights_backward_impl(__func__, b, n, m, k, P, Q, idx, temperature, min_sigma, weights, grad_weights, grad_Q, grad_P,
+                                      grad_sigma_partial, nullptr, false, stream);
+}
+
+extern "C" int sn_weighted_gather_forward(int b, int c, int n, int m, int k, const float *X, const int *idx,
+                                          const float *weights, float *out, sn_stream_t stream)
+{
+    SN_REQUIRE(b >= 0 && c >= 0 && n >= 1 && m >= 0 && k >= 1, "bad size");
+    if (b == 0 || m == 0 || c == 0) return 0;
+    SN_REQUIRE(X && idx && weights && out, "null pointer");
+    hipLaunchKernelGGL(weighted_gather_fwd_kernel, dim3(((size_t)c * m + 255) / 256, b), dim3(256), 0,
+                       (hipStream_t)stream, c, n, m, k, X, idx, weights, out);
+    SN_LAUNCH_CHECK();
+    return 0;
+}
+
+static int weighted_gather_backward_impl(const char *who, int b, int c, int n, int m, int k, const float *X, const int *idx,
+                                         const float *weights, const float *grad_out, float *grad_weights, float *grad_X,
+                                         float *scratch, bool ordered, sn_stream_t stream)
+{
+    SN_REQUIRE_AS(who, b >= 0 && c >= 0 && n >= 1 && m >= 0 && k >= 1, "bad size");
+    if (b == 0 || m == 0) return 0;
+    SN_REQUIRE_AS(who, X && idx && weights && grad_out && (!ordered || (grad_X && scratch)), "null pointer");
+    hipLaunchKernelGGL(weighted_gather_bwd_kernel, dim3(((size_t)m * k + 255) / 256, b), dim3(256), 0, (hipStream_t)stream, c, n, m,
+                       k, X, idx, weights, grad_out, grad_weights, grad_X, scratch);
+    if (ordered) return c == 0 ? 0 : launch_index_add<true>(who, b, n, c, (long long)m * k, idx, scratch, grad_X, (hipStream_t)stream);
+    SN_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+extern "C" int sn_weighted_gather_backward(int b, int c, int n, int m, int k, const float *X, const int *idx,
+                                           const float *weights, const float *grad_out, float *grad_weights,
+                                           float *grad_X, sn_stream_t stream)
+{
+    return weighted_gather_backward_impl(__func__, b, c, n, m, k, X, idx, weights, grad_out, grad_weights, grad_X, nullptr, false,
+                                         stream);
+}
+
 // The three backward entries above with the gradient towards the point cloud / the features summed in the ORDER of the
 // reference's CPU loops (query ascending, neighbour ascending) instead of by unordered float atomics: the kernels store the
 // per-(query, neighbour) contributions in `scratch` (b * m * k * 3 floats; b * c * m * k for the gather) and
@@ -1542,21 +1577,8 @@ extern "C" int sn_soft_project_backward_ordered(int b, int n, int m, int k, cons
                                                 const float *grad_proj, int gproj_layout, float *grad_Q, int gq_layout,
                                                 float *grad_P, float *grad_sigma_partial, float *scratch, sn_stream_t stream)
 {
-    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE((p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN) && (q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN),
-               "bad p_layout / q_layout");
-    SN_REQUIRE((gproj_layout == SN_LAYOUT_BNC || gproj_layout == SN_LAYOUT_BCN) && (gq_layout == SN_LAYOUT_BNC || gq_layout == SN_LAYOUT_BCN),
-               "bad gproj_layout / gq_layout");
-    SN_REQUIRE(P && Q && idx && temperature && grad_proj && grad_P && scratch, "null pointer");
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = p_layout, a.q_layout = q_layout, a.n = n, a.m = m, a.k = k;
-    a.grad_proj = grad_proj, a.gproj_layout = gproj_layout;
-    a.grad_Q = grad_Q, a.gq_layout = gq_layout, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
-    hipLaunchKernelGGL(soft_bwd_kernel<true>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    return p_layout == SN_LAYOUT_BNC ? launch_index_add<false>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream)
-                                     : launch_index_add<true>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    return soft_project_backward_impl(__func__, b, n, m, k, P, p_layout, Q, q_layout, idx, temperature, min_sigma, grad_proj,
+                                      gproj_layout, grad_Q, gq_layout, grad_P, grad_sigma_partial, scratch, true, stream);
 }
 
 extern "C" int sn_soft_weights_backward_ordered(int b, int n, int m, int k, const float *P, const float *Q, const int *idx,
@@ -1564,29 +1586,16 @@ extern "C" int sn_soft_weights_backward_ordered(int b, int n, int m, int k, cons
                                                 const float *grad_weights, float *grad_Q, float *grad_P,
                                                 float *grad_sigma_partial, float *scratch, sn_stream_t stream)
 {
-    SN_REQUIRE(b >= 0 && n >= 1 && m >= 0 && k >= 1 && k <= 64, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE(P && Q && idx && temperature && grad_weights && grad_P && scratch, "null pointer");
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = SN_LAYOUT_BCN, a.q_layout = SN_LAYOUT_BCN, a.n = n, a.m = m, a.k = k;
-    a.weights_in = weights, a.grad_weights = grad_weights;
-    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.grad_P = grad_P, a.gp_contrib = scratch, a.grad_sigma_partial = grad_sigma_partial;
-    hipLaunchKernelGGL(soft_bwd_kernel<false>, dim3(b, sn_soft_bwd_splits(b, m)), dim3(256), 0, (hipStream_t)stream, a);
-    return launch_index_add<true>(__func__, b, n, 3, (long long)m * k, idx, scratch, grad_P, (hipStream_t)stream);
+    return soft_weights_backward_impl(__func__, b, n, m, k, P, Q, idx, temperature, min_sigma, weights, grad_weights, grad_Q, grad_P,
+                                      grad_sigma_partial, scratch, true, stream);
 }
 
 extern "C" int sn_weighted_gather_backward_ordered(int b, int c, int n, int m, int k, const float *X, const int *idx,
                                                    const float *weights, const float *grad_out, float *grad_weights,
                                                    float *grad_X, float *scratch, sn_stream_t stream)
 {
-    SN_REQUIRE(b >= 0 && c >= 0 && n >= 1 && m >= 0 && k >= 1, "bad size");
-    if (b == 0 || m == 0) return 0;
-    SN_REQUIRE(X && idx && weights && grad_out && grad_X && scratch, "null pointer");
-    hipLaunchKernelGGL(weighted_gather_bwd_kernel, dim3(((size_t)m * k + 255) / 256, b), dim3(256), 0, (hipStream_t)stream, c, n, m,
-                       k, X, idx, weights, grad_out, grad_weights, grad_X, scratch);
-    if (c == 0) return 0;
-    return launch_index_add<true>(__func__, b, n, c, (long long)m * k, idx, scratch, grad_X, (hipStream_t)stream);
+    return weighted_gather_backward_impl(__func__, b, c, n, m, k, X, idx, weights, grad_out, grad_weights, grad_X, scratch, true,
+                                         stream);
 }
 
 extern "C" int sn_group_point(int b, int n, int c, int m, int nsample, const float *points, const int *idx,
@@ -1692,6 +1701,17 @@ __global__ void __launch_bounds__(1024) step_loss_partial_kernel(int M, int N, i
 
 __global__ void __launch_bounds__(64) step_loss_final_kernel(StepLossFinal f) { step_loss_final(f, threadIdx.x); }
 
+// the tail of both forward entries: the clouds' partials, in order, -> loss.  defer_value: the scalar is combined by an extra
+// wave of sn_sampler_step_loss_backward's first launch instead (the gradients do not need it; a launch of its own costs
+// ~4.7 us inside the step's graph) -- only for callers that always run backward
+static void launch_step_loss_final(int B, int M, int N, float weight, float alpha, float lmbda, float min_sigma,
+                                   const float *partial, const float *temperature, float *loss, int defer_value, hipStream_t st)
+{
+    if (defer_value) return;
+    const StepLossFinal f{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, partial, temperature, loss};
+    hipLaunchKernelGGL(step_loss_final_kernel, dim3(1), dim3(64), 0, st, f);
+}
+
 extern "C" int sn_sampler_step_loss_forward(int B, int M, int N, int G, const float *dist_q, const void *colmin_ws,
                                             const float *proj, const float *temperature, float alpha, float lmbda,
                                             float weight, float min_sigma, float *dist_p, int *idx_p, int *argmax1,
@@ -1702,12 +1722,7 @@ extern "C" int sn_sampler_step_loss_forward(int B, int M, int N, int G, const fl
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(step_loss_partial_kernel, dim3(B), dim3(1024), 0, st, M, N, G, 3 * M, dist_q, (const sn_u64 *)colmin_ws,
                        proj, dist_p, idx_p, partial, argmax1);
-    // defer_value: the scalar is combined by an extra wave of sn_sampler_step_loss_backward's first launch (the gradients do
-    // not need it; a launch of its own costs ~4.7 us inside the step's graph) -- only for callers that always run backward
-    if (!defer_value) {
-        const StepLossFinal f{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, partial, temperature, loss};
-        hipLaunchKernelGGL(step_loss_final_kernel, dim3(1), dim3(64), 0, st, f);
-    }
+    launch_step_loss_final(B, M, N, weight, alpha, lmbda, min_sigma, partial, temperature, loss, defer_value, st);
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -1757,12 +1772,51 @@ extern "C" int sn_sampler_step_loss_forward_direct(int B, int M, int N, const fl
     SN_REQUIRE(dist_q && dist_p && proj && temperature && argmax1 && partial && loss, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(step_loss_partial_direct_kernel, dim3(B), dim3(256), 0, st, M, N, 3 * M, dist_q, dist_p, proj, partial, argmax1);
-    if (!defer_value) {
-        const StepLossFinal f{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, partial, temperature, loss};
-        hipLaunchKernelGGL(step_loss_final_kernel, dim3(1), dim3(64), 0, st, f);
-    }
+    launch_step_loss_final(B, M, N, weight, alpha, lmbda, min_sigma, partial, temperature, loss, defer_value, st);
     SN_LAUNCH_CHECK();
     return 0;
+}
+
+// What both backward entries of the step hand to their kernels.  Implicit upstream gradients of the simplification loss -- same
+// roundings as the op-by-op route: (alpha * g) first, then the per-term coefficients.  argmax1: NULL in keys mode (the kernel
+// takes the farthest query from StepLossFold::qmax).
+static ImplicitGrad step_implicit_grad(int B, int N, int M, float weight, float alpha, const float *grad_loss, const int *argmax1)
+{
+    const float c1 = 1.0f / ((float)B * (float)M), cm = 1.0f / (float)B, c2 = weight / ((float)B * (float)N);
+    return ImplicitGrad{grad_loss, argmax1, nullptr, c1, cm, c2, 0.f, alpha};
+}
+
+// Soft-projection backward ADDED to grad_Q (B,3,M), sigma partials into gsig_scratch.  grad_proj (B,M,3), optional: the task
+// loss's gradient w.r.t. the projected points (main.py:507-531: the task network sits on proj); NULL = the benchmark's
+// stand-in term mean(proj) inside this loss, upstream gradient grad_loss / (3BM)
+static SoftBwdArgs step_soft_bwd_args(int B, int N, int M, int K, const float *P, const float *Q, const int *knn_idx,
+                                      const float *temperature, float min_sigma, const float *grad_loss, const float *grad_proj,
+                                      float *grad_Q, float *gsig_scratch)
+{
+    SoftBwdArgs a{};
+    a.P = P, a.Q = Q, a.idx = knn_idx, a.temperature = temperature, a.min_sigma = min_sigma;
+    a.p_layout = SN_LAYOUT_BNC, a.q_layout = SN_LAYOUT_BCN, a.n = N, a.m = M, a.k = K;
+    a.grad_proj = grad_proj, a.gproj_layout = SN_LAYOUT_BNC, a.gconst = grad_loss, a.gconst_div = (float)(B * 3 * M);
+    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.accumulate_q = 1;
+    a.grad_P = nullptr, a.grad_sigma_partial = gsig_scratch;
+    return a;
+}
+
+// alpha * d L_simp / d Q  +  d mean(proj) / d Q  (and the sigma partials) in one launch, N <= 2048.  fin: the deferred loss
+// value (an extra row of workgroups in the caller's grid); fold: the keys-mode operands; either may be empty.
+static void launch_chamfer_soft_bwd(dim3 grid, int M, int N, const float *Q, const float *P, const int *idx_q, const int *idx_p,
+                                    float *grad_Q, const ImplicitGrad &ig, const SoftBwdArgs &a, const StepLossFinal &fin,
+                                    const StepLossFold &fold, hipStream_t st)
+{
+    const dim3 block(256);
+    if (N <= 64)
+        hipLaunchKernelGGL(chamfer_soft_bwd_kernel<1>, grid, block, 0, st, M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, fold);
+    else if (N <= 256)
+        hipLaunchKernelGGL(chamfer_soft_bwd_kernel<4>, grid, block, 0, st, M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, fold);
+    else if (N <= 1024)
+        hipLaunchKernelGGL(chamfer_soft_bwd_kernel<16>, grid, block, 0, st, M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, fold);
+    else
+        hipLaunchKernelGGL(chamfer_soft_bwd_kernel<32>, grid, block, 0, st, M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, fold);
 }
 
 // grad_Q (B,3,M) channel-major (the FC head's layout), grad_T (1).  P: (B,N,3) only -- any p_layout but SN_LAYOUT_BNC is refused
@@ -1781,39 +1835,19 @@ extern "C" int sn_sampler_step_loss_backward(int B, int N, int M, int K, const f
     SN_REQUIRE(P && Q && knn_idx && idx_q && idx_p && argmax1 && temperature && grad_loss && grad_Q && gsig_scratch && grad_T,
                "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    // same roundings as the op-by-op route: (alpha * g) first, then the per-term coefficients
-    const float c1 = 1.0f / ((float)B * (float)M), cm = 1.0f / (float)B, c2 = weight / ((float)B * (float)N);
-    ImplicitGrad ig{grad_loss, argmax1, nullptr, c1, cm, c2, 0.f, alpha};
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = knn_idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = p_layout, a.q_layout = SN_LAYOUT_BCN, a.n = N, a.m = M, a.k = K;
-    a.grad_proj = nullptr, a.gconst = grad_loss, a.gconst_div = (float)(B * 3 * M);
-    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.accumulate_q = 1;
-    a.grad_P = nullptr, a.grad_sigma_partial = gsig_scratch;
-    int splits = sn_soft_bwd_splits(B, M);
+    const ImplicitGrad ig = step_implicit_grad(B, N, M, weight, alpha, grad_loss, argmax1);
+    const SoftBwdArgs a = step_soft_bwd_args(B, N, M, K, P, Q, knn_idx, temperature, min_sigma, grad_loss, nullptr, grad_Q, gsig_scratch);
+    const int splits = sn_soft_bwd_splits(B, M);  // gsig_scratch is sized by the caller for that many
+    const StepLossFinal fin{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, deferred_partial, temperature, deferred_loss};
     if (N <= 2048) {
-        // 1+2. alpha * d L_simp / d Q  +  d mean(proj) / d Q  (and the sigma partials) in one launch
-        splits = std::max(1, std::min((M + 3) / 4, (kChamferBwdGroups + B - 1) / B));
-        splits = std::min(splits, sn_soft_bwd_splits(B, M));  // gsig_scratch is sized by the caller for that many
-        const StepLossFinal fin{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, deferred_partial, temperature, deferred_loss};
-        const dim3 grid(B, splits + (deferred_loss ? 1 : 0)), block(256);
-#define SN_CS(PPL_) \
-    hipLaunchKernelGGL(chamfer_soft_bwd_kernel<PPL_>, grid, block, 0, st, M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, StepLossFold{})
-        if (N <= 64) SN_CS(1);
-        else if (N <= 256) SN_CS(4);
-        else if (N <= 1024) SN_CS(16);
-        else SN_CS(32);
-#undef SN_CS
+        // 1+2. in one launch; the deferred loss value in an extra row of workgroups
+        launch_chamfer_soft_bwd(dim3(B, splits + (deferred_loss ? 1 : 0)), M, N, Q, P, idx_q, idx_p, grad_Q, ig, a, fin, StepLossFold{}, st);
     } else {
         // 1. alpha * d L_simp / d Q   (targets = Q, channel-major; sources = P)
-        auto ysplit = [&](int nt) { return std::max(1, std::min((nt + 3) / 4, (kChamferBwdGroups + B - 1) / B)); };
-        launch_chamfer_bwd(B, ysplit(M), M, N, Q, P, nullptr, idx_q, nullptr, idx_p, grad_Q, 1, ig, st, 1);
+        launch_chamfer_bwd(B, splits, M, N, Q, P, nullptr, idx_q, nullptr, idx_p, grad_Q, 1, ig, st, 1);
         // 2. + d mean(proj) / d Q, and the sigma partials
         hipLaunchKernelGGL(soft_bwd_kernel<true>, dim3(B, splits), dim3(256), 0, st, a);
-        if (deferred_loss) {
-            const StepLossFinal fin{B, M, N, 3 * M, weight, alpha, lmbda, min_sigma, deferred_partial, temperature, deferred_loss};
-            hipLaunchKernelGGL(step_loss_final_kernel, dim3(1), dim3(64), 0, st, fin);
-        }
+        if (deferred_loss) hipLaunchKernelGGL(step_loss_final_kernel, dim3(1), dim3(64), 0, st, fin);
     }
     // 3. grad_T from the sigma partials and the direct lmbda * sigma term
     hipLaunchKernelGGL(sigma_grad_kernel, dim3(1), dim3(256), 0, st, B * splits, gsig_scratch, temperature, min_sigma, grad_T,
@@ -1839,29 +1873,12 @@ extern "C" int sn_sampler_step_loss_keys(int B, int N, int M, int K, const float
                "null pointer");
     if (N > 2048) return sn_set_error(SN_ERR_UNSUPPORTED, "sn_sampler_step_loss_keys: N <= 2048");
     hipStream_t st = (hipStream_t)stream;
-    const float c1 = 1.0f / ((float)B * (float)M), cm = 1.0f / (float)B, c2 = weight / ((float)B * (float)N);
-    ImplicitGrad ig{grad_loss, nullptr, nullptr, c1, cm, c2, 0.f, alpha};
-    SoftBwdArgs a{};
-    a.P = P, a.Q = Q, a.idx = knn_idx, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.p_layout = p_layout, a.q_layout = SN_LAYOUT_BCN, a.n = N, a.m = M, a.k = K;
-    // grad_proj (B,M,3), optional: the task loss's gradient w.r.t. the projected points (main.py:507-531: the task network
-    // sits on proj); NULL = the benchmark's stand-in term mean(proj) inside this loss, upstream gradient grad_loss / (3BM)
-    a.grad_proj = grad_proj, a.gproj_layout = SN_LAYOUT_BNC, a.gconst = grad_loss, a.gconst_div = (float)(B * 3 * M);
-    a.grad_Q = grad_Q, a.gq_layout = SN_LAYOUT_BCN, a.accumulate_q = 1;
-    a.grad_P = nullptr, a.grad_sigma_partial = gsig_scratch;
-    int splits = std::max(1, std::min((M + 3) / 4, (kChamferBwdGroups + B - 1) / B));
-    splits = std::min(splits, sn_soft_bwd_splits(B, M));
+    const ImplicitGrad ig = step_implicit_grad(B, N, M, weight, alpha, grad_loss, nullptr);
+    const SoftBwdArgs a = step_soft_bwd_args(B, N, M, K, P, Q, knn_idx, temperature, min_sigma, grad_loss, grad_proj, grad_Q, gsig_scratch);
+    const int splits = sn_soft_bwd_splits(B, M);  // gsig_scratch is sized by the caller for that many
     StepLossFold fold{};
     fold.G = G, fold.keys = (const sn_u64 *)colmin_keys, fold.qmax = (const sn_u64 *)qmax, fold.dpsum = dpsum;
-    const dim3 grid(B, splits), block(256);
-#define SN_CS(PPL_)                                                                                                        \
-    hipLaunchKernelGGL(chamfer_soft_bwd_kernel<PPL_>, grid, block, 0, st, M, N, Q, P, idx_q, (const int *)nullptr, grad_Q, ig, a, \
-                       StepLossFinal{}, fold)
-    if (N <= 64) SN_CS(1);
-    else if (N <= 256) SN_CS(4);
-    else if (N <= 1024) SN_CS(16);
-    else SN_CS(32);
-#undef SN_CS
+    launch_chamfer_soft_bwd(dim3(B, splits), M, N, Q, P, idx_q, nullptr, grad_Q, ig, a, StepLossFinal{}, fold, st);
     const StepLossKeysFinal kf{B, G, M, N, 3 * M, weight, alpha, lmbda, min_sigma, qpart, (const sn_u64 *)qmax, dpsum, temperature,
                                loss, (sn_u64 *)colmin_keys, (long long)B * N, grad_proj ? 0 : 1, {nullptr, nullptr}};
     if (deferred_tail) {

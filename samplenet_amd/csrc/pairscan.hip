@@ -608,12 +608,15 @@ static int launch_pairscan(const PairscanArgs &a, int waves, int ysplit, hipStre
     return 0;
 }
 
+// points of the cloud that a lane holds in registers on the single-chunk path (N <= 2048): the instantiated PPL
+static int points_per_lane(int N) { return N <= 64 ? 1 : (N <= 256 ? 4 : (N <= 1024 ? 16 : 32)); }
+
 // number of workgroups the queries of one cloud are spread over (single-chunk path, N <= 2048): the batch alone cannot
 // fill the chip at B = 32, so aim at >= 2 workgroups per CU
 int pairscan_ysplit(int B, int N, int M, bool colmin)
 {
     if (N > kWave * 32) return 1;
-    const int ppl = N <= 64 ? 1 : (N <= 256 ? 4 : (N <= 1024 ? 16 : 32));
+    const int ppl = points_per_lane(N);
     const int maxw = max_threads(ppl, colmin) / kWave;
     const int want = (512 + B - 1) / std::max(B, 1);
     return std::max(1, std::min(want, (M + maxw - 1) / maxw));
@@ -628,7 +631,7 @@ int pairscan_dispatch(PairscanArgs a, void *ws, long long ws_bytes, bool finaliz
     if (used_split) *used_split = 1;
     if (N <= kWave * 32) {
         // single chunk: the whole cloud lives in the wave's registers
-        const int ppl = N <= 64 ? 1 : (N <= 256 ? 4 : (N <= 1024 ? 16 : 32));
+        const int ppl = points_per_lane(N);
         const int maxw = max_threads(ppl, colmin) / kWave;
         int ysplit = pairscan_ysplit(a.B, N, M, colmin);
         if (colmin && ysplit > 1 && !a.colmin_keys) {
@@ -774,6 +777,39 @@ extern "C" int sn_pairscan_colmin_splits(int B, int N, int M)
     return sn::pairscan_ysplit(B, N, M, true);
 }
 
+// the body of the sampler step's three scans, behind each entry's own size and pointer checks.  Queries: Q, or -- fc_w != NULL --
+// produced in the scan by the head's last layer and written to q_out.  Per-point minima: combined in colmin_keys (with
+// qpart / qmax), else left as G partial key sets in the workspace.
+static int pairscan_step_impl(const char *who, int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
+                              int q_layout, const float *fc_z, const float *fc_scale, const float *fc_shift, const float *fc_w,
+                              const float *fc_bias, int Kfc, float *q_out, int *knn_idx, float *dist_q, int *idx_q, float *proj,
+                              int proj_layout, const float *temperature, float min_sigma, void *workspace,
+                              long long workspace_bytes, void *colmin_keys, float *qpart, void *qmax, sn_stream_t stream)
+{
+    SN_REQUIRE_AS(who, p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
+    SN_REQUIRE_AS(who, q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN, "bad q_layout");
+    const int G = sn_pairscan_colmin_splits(B, N, M);
+    if (G <= 1 || N > sn::kWave * 32)
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: this shape runs as one workgroup per cloud", who);
+    if (!colmin_keys) SN_REQUIRE_AS(who, workspace_bytes >= (long long)B * G * N * 8, "workspace too small");
+    PairscanArgs a{};
+    a.P = P, a.Q = Q, a.p_layout = p_layout, a.q_layout = q_layout;
+    a.B = B, a.N = N, a.M = M, a.K = K;
+    a.knn_idx = knn_idx, a.dist_q = dist_q, a.idx_q = idx_q;
+    a.proj = proj, a.proj_layout = proj_layout, a.temperature = temperature, a.min_sigma = min_sigma;
+    if (fc_w) {
+        a.fc_z = fc_z, a.fc_scale = fc_scale, a.fc_shift = fc_shift, a.fc_w = fc_w, a.fc_bias = fc_bias, a.fc_k = Kfc;
+        a.q_out = q_out;
+    }
+    a.colmin_keys = (sn_u64 *)colmin_keys, a.qpart = qpart, a.qmax = (sn_u64 *)qmax;
+    int used = 0;
+    int rc = sn::pairscan_dispatch(a, workspace, workspace_bytes, false, &used, (hipStream_t)stream);
+    if (rc) return rc;
+    SN_LAUNCH_CHECK_AS(who);  // (first: SN_REQUIRE discards the pending launch status)
+    if (used != G) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: internal: split mismatch", who);
+    return 0;
+}
+
 extern "C" int sn_pairscan_forward_partial(int B, int N, int M, int K, const float *P, int p_layout, const float *Q,
                                            int q_layout, int *knn_idx, float *dist_q, int *idx_q, float *proj,
                                            int proj_layout, const float *temperature, float min_sigma, void *workspace,
@@ -781,23 +817,9 @@ extern "C" int sn_pairscan_forward_partial(int B, int N, int M, int K, const flo
 {
     SN_REQUIRE(B >= 1 && N >= 1 && M >= 1 && K >= 1 && K <= 64 && K <= N, "bad size");
     SN_REQUIRE(P && Q && workspace && temperature, "null pointer");
-    SN_REQUIRE(p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
-    SN_REQUIRE(q_layout == SN_LAYOUT_BNC || q_layout == SN_LAYOUT_BCN, "bad q_layout");
-    const int G = sn_pairscan_colmin_splits(B, N, M);
-    if (G <= 1 || N > sn::kWave * 32)
-        return sn_set_error(SN_ERR_UNSUPPORTED, "sn_pairscan_forward_partial: this shape runs as one workgroup per cloud");
-    SN_REQUIRE(workspace_bytes >= (long long)B * G * N * 8, "workspace too small");
-    PairscanArgs a{};
-    a.P = P, a.Q = Q, a.p_layout = p_layout, a.q_layout = q_layout;
-    a.B = B, a.N = N, a.M = M, a.K = K;
-    a.knn_idx = knn_idx, a.dist_q = dist_q, a.idx_q = idx_q;
-    a.proj = proj, a.proj_layout = proj_layout, a.temperature = temperature, a.min_sigma = min_sigma;
-    int used = 0;
-    int rc = sn::pairscan_dispatch(a, workspace, workspace_bytes, false, &used, (hipStream_t)stream);
-    if (rc) return rc;
-    SN_LAUNCH_CHECK();  // (first: SN_REQUIRE discards the pending launch status)
-    if (used != G) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: internal: split mismatch", __func__);
-    return 0;
+    return pairscan_step_impl(__func__, B, N, M, K, P, p_layout, Q, q_layout, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                              knn_idx, dist_q, idx_q, proj, proj_layout, temperature, min_sigma, workspace, workspace_bytes,
+                              nullptr, nullptr, nullptr, stream);
 }
 
 // sn_chamfer_forward on a batch whose SMALLER clouds are padded with cyclic copies (sn_cyclic_pad_cat): only the first
@@ -835,26 +857,9 @@ extern "C" int sn_pairscan_forward_keys(int B, int N, int M, int K, const float 
     SN_REQUIRE(B >= 1 && N >= 1 && M >= 1 && K >= 1 && K <= 64 && K <= N, "bad size");
     SN_REQUIRE(P && Q && dist_q && proj && temperature && colmin_keys && qpart && qmax, "null pointer");
     SN_REQUIRE(!fc_w || (fc_z && fc_scale && fc_shift && fc_bias && Kfc >= 4 && Kfc % 4 == 0), "bad fc operands");
-    SN_REQUIRE(p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
-    const int G = sn_pairscan_colmin_splits(B, N, M);
-    if (G <= 1 || N > sn::kWave * 32)
-        return sn_set_error(SN_ERR_UNSUPPORTED, "sn_pairscan_forward_keys: this shape runs as one workgroup per cloud");
-    PairscanArgs a{};
-    a.P = P, a.Q = Q, a.p_layout = p_layout, a.q_layout = SN_LAYOUT_BCN;
-    a.B = B, a.N = N, a.M = M, a.K = K;
-    a.knn_idx = knn_idx, a.dist_q = dist_q, a.idx_q = idx_q;
-    a.proj = proj, a.proj_layout = proj_layout, a.temperature = temperature, a.min_sigma = min_sigma;
-    if (fc_w) {
-        a.fc_z = fc_z, a.fc_scale = fc_scale, a.fc_shift = fc_shift, a.fc_w = fc_w, a.fc_bias = fc_bias, a.fc_k = Kfc;
-        a.q_out = Q;
-    }
-    a.colmin_keys = (sn_u64 *)colmin_keys, a.qpart = qpart, a.qmax = (sn_u64 *)qmax;
-    int used = 0;
-    int rc = sn::pairscan_dispatch(a, nullptr, 0, false, &used, (hipStream_t)stream);
-    if (rc) return rc;
-    SN_LAUNCH_CHECK();  // (first: SN_REQUIRE discards the pending launch status)
-    if (used != G) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: internal: split mismatch", __func__);
-    return 0;
+    return pairscan_step_impl(__func__, B, N, M, K, P, p_layout, Q, SN_LAYOUT_BCN, fc_z, fc_scale, fc_shift, fc_w, fc_bias, Kfc, Q,
+                              knn_idx, dist_q, idx_q, proj, proj_layout, temperature, min_sigma, nullptr, 0, colmin_keys, qpart,
+                              qmax, stream);
 }
 
 // sn_pairscan_forward_partial whose queries are produced in the scan itself by the head's last fully connected layer
@@ -870,24 +875,9 @@ extern "C" int sn_pairscan_forward_partial_fc(int B, int N, int M, int K, const 
     SN_REQUIRE(B >= 1 && N >= 1 && M >= 1 && K >= 1 && K <= 64 && K <= N, "bad size");
     SN_REQUIRE(P && fc_z && fc_scale && fc_shift && fc_w && fc_bias && q_out && workspace && temperature, "null pointer");
     SN_REQUIRE(Kfc >= 4 && Kfc % 4 == 0, "Kfc must be a multiple of 4");
-    SN_REQUIRE(p_layout == SN_LAYOUT_BNC || p_layout == SN_LAYOUT_BCN, "bad p_layout");
-    const int G = sn_pairscan_colmin_splits(B, N, M);
-    if (G <= 1 || N > sn::kWave * 32)
-        return sn_set_error(SN_ERR_UNSUPPORTED, "sn_pairscan_forward_partial_fc: this shape runs as one workgroup per cloud");
-    SN_REQUIRE(workspace_bytes >= (long long)B * G * N * 8, "workspace too small");
-    PairscanArgs a{};
-    a.P = P, a.Q = q_out, a.p_layout = p_layout, a.q_layout = SN_LAYOUT_BCN;
-    a.B = B, a.N = N, a.M = M, a.K = K;
-    a.knn_idx = knn_idx, a.dist_q = dist_q, a.idx_q = idx_q;
-    a.proj = proj, a.proj_layout = proj_layout, a.temperature = temperature, a.min_sigma = min_sigma;
-    a.fc_z = fc_z, a.fc_scale = fc_scale, a.fc_shift = fc_shift, a.fc_w = fc_w, a.fc_bias = fc_bias, a.fc_k = Kfc;
-    a.q_out = q_out;
-    int used = 0;
-    int rc = sn::pairscan_dispatch(a, workspace, workspace_bytes, false, &used, (hipStream_t)stream);
-    if (rc) return rc;
-    SN_LAUNCH_CHECK();  // (first: SN_REQUIRE discards the pending launch status)
-    if (used != G) return sn_set_error(SN_ERR_BAD_ARGUMENT, "%s: internal: split mismatch", __func__);
-    return 0;
+    return pairscan_step_impl(__func__, B, N, M, K, P, p_layout, q_out, SN_LAYOUT_BCN, fc_z, fc_scale, fc_shift, fc_w, fc_bias, Kfc,
+                              q_out, knn_idx, dist_q, idx_q, proj, proj_layout, temperature, min_sigma, workspace, workspace_bytes,
+                              nullptr, nullptr, nullptr, stream);
 }
 
 #ifdef SN_PS_TIMELINE

@@ -204,10 +204,10 @@ class SamplerTrainStep:
             # classification: a BatchNorm on the head's output): the single-node LOSS applies to them as it is (the head runs through
             # net._features, the temperature through the module's own clamp); the fc4-in-scan / outside-task forms do not
             return False
-        from ._lib import lib
+        from . import ops
 
         B, N, _ = self.x.shape
-        split = lib.sn_pairscan_colmin_splits(B, N, net.num_out_points) > 1
+        split = ops.scan_splits(B, N, net.num_out_points) > 1
         if self.task_loss is None:
             # (batches that fill the chip with one workgroup per cloud: same single-node loss behind the plain scan -- fc4 as a
             #  launch of its own, per-cloud loss partials; ops.step_loss_forward)
@@ -280,7 +280,7 @@ class SamplerTrainStep:
                 T = torch.clamp(T.detach(), min=net.project._temperature_floor)
             elif floor:
                 T = net.project._t()  # max(T, floor): the kernels square what they are given; its gradient gate is autograd's
-            if std and self.fused_head and net.use_hip_mlp and ops.lib.sn_pairscan_colmin_splits(B, N, net.num_out_points) > 1:
+            if std and self.fused_head and net.use_hip_mlp and ops.scan_splits(B, N, net.num_out_points) > 1:
                 from .fused_step import sampler_step
 
                 loss, y, proj = sampler_step(net, x, self.alpha, self.lmbda, weight, t_sink, True)  # fc4 inside the scan

@@ -18,7 +18,8 @@ from . import ops, pointnet
 
 # Test hooks (no environment switches; the defaults are the product path).  KEYS_LOSS: per-point minima combined across a
 # cloud's scan workgroups by atomicMax on inverted keys -- no reduction launch between the scan and the backward
-# (sn_pairscan_forward_keys / sn_sampler_step_loss_keys); False = the partial-key route every N > 2048 batch takes.
+# (sn_pairscan_forward_keys / sn_sampler_step_loss_keys); False = the partial-key route: G key sets per cloud and a reduction
+# launch, which serves split clouds (G > 1) without a key table (N > 2048 never splits: one workgroup per cloud scans it).
 # DEFER_TAIL: the loss side's scalar tail (sigma gradient, loss value, key-table reset) rides in the closing kernel of the conv
 # stack's backward instead of a launch of its own; False = the route unsupported conv-stack shapes take.
 KEYS_LOSS = True
@@ -60,7 +61,7 @@ class SamplerStepFunction(torch.autograd.Function):
                 y, fc = yo.view(B, 3, M), None
             keys = None
             token = None
-            if defer_value and KEYS_LOSS and x.shape[1] <= 2048:
+            if defer_value and ops.keys_step_possible(B, x.shape[1], M):
                 # persistent zeroed table of inverted per-point keys (every step's backward leaves it zero again).  It belongs
                 # to ONE forward at a time: a second forward before the owner's backward (two sampler passes under one loss,
                 # main.py:516-524) gets a private table instead of clobbering the owner's minima; an owner that was dropped
@@ -82,7 +83,7 @@ class SamplerStepFunction(torch.autograd.Function):
                                                       keys=keys)
         ctx.net, ctx.saved, ctx.state = net, saved, state
         ctx.x, ctx.y, ctx.temperature = x, y, temperature
-        ctx.cfg = (K, float(min_sigma), float(alpha), float(lmbda), float(weight))
+        ctx.cfg = ops.StepCfg(K, float(min_sigma), float(alpha), float(lmbda), float(weight))
         ctx.t_sink = t_sink
         ctx.keys_token = token
         ctx.mean_proj = bool(mean_proj)
@@ -110,21 +111,21 @@ class SamplerStepFunction(torch.autograd.Function):
             if grad_loss is None:
                 grad_loss = torch.zeros((), device=ctx.y.device)
         sink, owner = pointnet.sink_for_backward(net)
-        if len(ctx.state) > 5 and ctx.state[5][0] == "keys":
+        keys_mode = ctx.state.keys_mode
+        if keys_mode:
             if getattr(ctx, "keys_consumed", False):
                 raise RuntimeError("SamplerStepFunction: the key table of this forward was already consumed by a backward "
                                    "(call the step again instead of backpropagating one forward twice)")
             ctx.keys_consumed = True
         with torch.cuda.device(ctx.y.device):
-            keys_mode = len(ctx.state) > 5 and ctx.state[5][0] == "keys"
             # keys mode: the sigma-gradient / loss-value / key-reset work rides in the closing kernel of the conv stack's backward
             blob = None
             if keys_mode and DEFER_TAIL and pointnet.conv_stack_backward_supported(net, ctx.x.shape[0], ctx.x.shape[1]):
                 import ctypes
 
                 blob = ctypes.create_string_buffer(ops.lib.sn_step_tail_bytes())
-            res = ops.step_loss_backward(ctx.x, ctx.y, ctx.temperature, ctx.state, ctx.cfg, grad_loss, ctx.t_sink, blob, gproj)
-            gQ, gT = res[0], res[1]
+            gQ, gT, keep = ops.step_loss_backward(ctx.x, ctx.y, ctx.temperature, ctx.state, ctx.cfg, grad_loss, ctx.t_sink, blob,
+                                                  gproj)
             if keys_mode:  # (the backward's last launch re-zeroed the key table: hand the persistent one back)
                 kown = getattr(net, "_colmin_keys_owner", None)
                 if kown is not None and kown() is ctx.keys_token:
@@ -133,7 +134,7 @@ class SamplerStepFunction(torch.autograd.Function):
                                            getattr(net, "_after_fc_grads", None) if sink is not None else None, step_tail=blob)
             if owner is not None:
                 owner.commit(None if sink is not None else grads)
-            del res, gproj  # (scratch the deferred tail reads: released only behind the conv backward)
+            del keep, gproj  # (scratch the deferred tail reads: released only behind the conv backward)
         g_temp = None
         if ctx.t_sink is None and ctx.needs_input_grad[2]:
             g_temp = gT.reshape(ctx.temperature.shape)
@@ -157,7 +158,7 @@ def external_task_supported(net, x_bnc):
     """True when sampler_step(..., defer_value=True, mean_proj=False) can run this batch (keys-mode scan: N <= 2048 and a batch
     small enough that clouds are split over workgroups)."""
     B, N, _ = x_bnc.shape
-    return bool(KEYS_LOSS and N <= 2048 and ops.lib.sn_pairscan_colmin_splits(B, N, net.num_out_points) > 1)
+    return ops.keys_step_possible(B, N, net.num_out_points)
 
 
 class _DirectCtx:

@@ -4,6 +4,8 @@ Host-side plumbing only -- allocation of outputs with torch, stream / device sel
 bookkeeping.  All arithmetic happens in the HIP kernels (samplenet_amd/csrc).  Every function
 requires CUDA(HIP) tensors and raises otherwise: there is no CPU path in the product.
 """
+from typing import NamedTuple
+
 import torch
 
 from ._lib import check, lib, ptr, stream_of
@@ -787,6 +789,48 @@ class SamplerLossFunction(torch.autograd.Function):
         return gls.reshape(lshape), gT.reshape(temperature.shape), gproj, None, None, None
 
 
+class StepCfg(NamedTuple):
+    """The step loss's constants, as step_loss_backward takes them."""
+
+    K: int
+    min_sigma: float
+    alpha: float
+    lmbda: float
+    weight: float
+
+
+class StepLossState:
+    """What step_loss_forward hands to step_loss_backward.  idx (B,M,K): the kNN indices; idx_q (B,M) / idx_p (B,N): the nearest
+    point of every query / the nearest query of every point; argmax1 (B,).  deferred: (partial, loss) when the backward's first
+    launch writes the loss value, else (None, None).  Keys mode (the per-point minima stay in the caller's key table, the
+    backward produces idx_p / argmax1 itself: both None here): keys, qpart, qmax and G, the scan workgroups per cloud; None
+    on the other routes."""
+
+    __slots__ = ("idx", "idx_q", "idx_p", "argmax1", "deferred", "keys", "qpart", "qmax", "G")
+
+    def __init__(self, idx, idx_q, idx_p, argmax1, deferred, keys=None, qpart=None, qmax=None, G=None):
+        self.idx, self.idx_q, self.idx_p, self.argmax1, self.deferred = idx, idx_q, idx_p, argmax1, deferred
+        self.keys, self.qpart, self.qmax, self.G = keys, qpart, qmax, G
+
+    @property
+    def keys_mode(self):
+        return self.keys is not None
+
+
+def scan_splits(B, N, M):
+    """Scan workgroups per cloud (pairscan_ysplit): 1 = the one-workgroup-per-cloud scan finishes the per-point minima itself
+    (batches that fill the chip, and every N > 2048); above 1 a cloud's per-point minima are combined behind the scan."""
+    return lib.sn_pairscan_colmin_splits(B, N, M)
+
+
+def keys_step_possible(B, N, M):
+    """True when the batch can run the keys-mode step: clouds split over workgroups, N within the key table's bound, and the
+    test hook fused_step.KEYS_LOSS left on."""
+    from . import fused_step
+
+    return bool(fused_step.KEYS_LOSS and N <= 2048 and scan_splits(B, N, M) > 1)
+
+
 class SamplerStepLossFunction(torch.autograd.Function):
     """The whole loss side of the sampler's training step behind ONE autograd node (engine fast path):
         simp = y (B,3,M) from the FC head;  proj = SoftProjection(x, simp)                       (soft_projection.py:138-152)
@@ -803,9 +847,9 @@ class SamplerStepLossFunction(torch.autograd.Function):
         y, x = _f32c(y_bcn), _f32c(x_bnc)
         with torch.cuda.device(y.device):
             loss, proj, state = step_loss_forward(x, y, None, temperature, K, min_sigma, alpha, lmbda, weight, defer_value)
-        ctx.save_for_backward(x, y, temperature, *state[:4])
-        ctx.deferred = state[4]
-        ctx.cfg = (K, float(min_sigma), float(alpha), float(lmbda), float(weight))
+        ctx.save_for_backward(x, y, temperature, state.idx, state.idx_q, state.idx_p, state.argmax1)
+        ctx.deferred = state.deferred
+        ctx.cfg = StepCfg(K, float(min_sigma), float(alpha), float(lmbda), float(weight))
         ctx.t_sink = t_sink
         ctx.mark_non_differentiable(proj)
         ctx.set_materialize_grads(False)
@@ -817,7 +861,8 @@ class SamplerStepLossFunction(torch.autograd.Function):
         if grad_loss is None:
             return (None,) * 10
         with torch.cuda.device(y.device):
-            gQ, gT = step_loss_backward(x, y, temperature, (idx, iq, ip, argmax1, ctx.deferred), ctx.cfg, grad_loss, ctx.t_sink)
+            state = StepLossState(idx, iq, ip, argmax1, ctx.deferred)
+            gQ, gT, _ = step_loss_backward(x, y, temperature, state, ctx.cfg, grad_loss, ctx.t_sink)
         g_temp = None
         if ctx.t_sink is None and ctx.needs_input_grad[2]:
             g_temp = gT.reshape(temperature.shape)
@@ -828,14 +873,14 @@ def step_loss_forward(x, y, fc, temperature, K, min_sigma, alpha, lmbda, weight,
     """Forward launches of the sampler step's loss side (SamplerStepLossFunction / fused_step.SamplerStepFunction).
     x (B,N,3), y (B,3,M): the simplified cloud -- read when fc is None, otherwise WRITTEN by the pair scan from
     fc = (z3 (B,Kfc), coef3 (>=2*Kfc: scale | shift), W4 (3M,Kfc), b4 (3M)).  Caller holds the device guard.
-    -> loss (2,), proj (B,M,3), state = (idx, iq, ip, argmax1, (partial, loss) | (None, None)[, keys-mode record]).
+    -> loss (2,), proj (B,M,3), state (a StepLossState).
     keys (needs N <= 2048; the backward must follow): zeroed (B*N) int64 table; only the pair scan runs here, the per-point
     minima are combined in the table and the loss value is produced by the backward's launches (sn_sampler_step_loss_keys).
     proj_out: a preallocated contiguous (B,M,3) fp32 tensor for the projected cloud (the captured surface's output block)."""
     B, _, M = y.shape
     N = x.shape[1]
     dev = y.device
-    G = lib.sn_pairscan_colmin_splits(B, N, M)
+    G = scan_splits(B, N, M)
     if G <= 1 and (fc is not None or keys is not None):
         raise ValueError("fc4 inside the scan / the keys-mode step need a batch small enough for split clouds")
     proj = proj_out if proj_out is not None else torch.empty(B, M, 3, device=dev, dtype=torch.float32)
@@ -859,7 +904,7 @@ def step_loss_forward(x, y, fc, temperature, K, min_sigma, alpha, lmbda, weight,
         check(lib.sn_sampler_step_loss_forward_direct(B, M, N, ptr(dq), ptr(dp), ptr(proj), ptr(T), float(alpha), float(lmbda),
                                                       float(weight), float(min_sigma), ptr(argmax1), ptr(partial), ptr(loss),
                                                       1 if defer_value else 0, st), "sn_sampler_step_loss_forward_direct")
-        return loss, proj, (idx, iq, ip, argmax1, (partial, loss) if defer_value else (None, None))
+        return loss, proj, StepLossState(idx, iq, ip, argmax1, (partial, loss) if defer_value else (None, None))
     ws = torch.empty(B * G * N, device=dev, dtype=torch.int64)
     partial = torch.empty(B * 4, device=dev, dtype=torch.float32)
     loss = torch.empty(2, device=dev, dtype=torch.float32)
@@ -876,7 +921,7 @@ def step_loss_forward(x, y, fc, temperature, K, min_sigma, alpha, lmbda, weight,
                                            (coef3.data_ptr() + 4 * Kfc) if fc is not None else None, ptr(W4), ptr(b4), Kfc,
                                            ptr(idx), ptr(dq), ptr(iq), ptr(proj), BNC, ptr(T), float(min_sigma), ptr(keys),
                                            ptr(qpart), ptr(qmax), st), "sn_pairscan_forward_keys")
-        return loss, proj, (idx, iq, None, None, (partial, loss), ("keys", keys, qpart, qmax, G))
+        return loss, proj, StepLossState(idx, iq, None, None, (partial, loss), keys, qpart, qmax, G)
     if fc is None:
         check(lib.sn_pairscan_forward_partial(B, N, M, K, ptr(x), BNC, ptr(y), BCN, ptr(idx), ptr(dq), ptr(iq), ptr(proj), BNC,
                                               ptr(T), float(min_sigma), ptr(ws), ws.numel() * 8, st),
@@ -892,16 +937,18 @@ def step_loss_forward(x, y, fc, temperature, K, min_sigma, alpha, lmbda, weight,
                                            float(weight), float(min_sigma), ptr(dp), ptr(ip), ptr(argmax1), ptr(partial),
                                            ptr(loss), 1 if defer_value else 0, st), "sn_sampler_step_loss_forward")
     # defer_value: the loss VALUE is written by the backward's first launch (engine: backward always follows)
-    return loss, proj, (idx, iq, ip, argmax1, (partial, loss) if defer_value else (None, None))
+    return loss, proj, StepLossState(idx, iq, ip, argmax1, (partial, loss) if defer_value else (None, None))
 
 
 def step_loss_backward(x, y, temperature, state, cfg, grad_loss, t_sink, deferred_tail=None, grad_proj=None, grad_sigma=None):
-    """Backward launches of the sampler step's loss side -> (grad_Q (B,3,M), grad_T (1,)).  Caller holds the device guard.
+    """Backward launches of the sampler step's loss side -> (grad_Q (B,3,M), grad_T (1,), keep).  Caller holds the device guard.
+    state: step_loss_forward's StepLossState; cfg: a StepCfg.  keep: the scratch a deferred tail still reads -- the caller holds
+    it until that launch (the closing kernel of the conv backward) is enqueued -- or None.
     grad_proj (B,M,3), keys mode only: gradient of an outside task loss w.r.t. the projected points; the step's own loss then
     has no mean(proj) term (None: that stand-in term is part of the loss, its gradient implicit).
     grad_sigma (1,), keys mode only: upstream gradient of sigma as an output of its own (the drop-in surface); the direct term of
     grad_T is then grad_sigma * d sigma / dT instead of lmbda * grad_loss * d sigma / dT."""
-    idx, iq, ip, argmax1, (dpart, dloss) = state[:5]
+    dpart, dloss = state.deferred
     K, min_sigma, alpha, lmbda, weight = cfg
     B, _, M = y.shape
     N = x.shape[1]
@@ -911,22 +958,19 @@ def step_loss_backward(x, y, temperature, state, cfg, grad_loss, t_sink, deferre
     gT = t_sink if t_sink is not None else torch.empty(1, device=dev, dtype=torch.float32)
     gl = grad_loss.contiguous().float().reshape(1)
     T = temperature.detach().float().reshape(1)
-    if len(state) > 5 and state[5][0] == "keys":
-        _, keys, qpart, qmax, G = state[5]
-        check(lib.sn_sampler_step_loss_keys(B, N, M, K, ptr(x), BNC, ptr(y), ptr(idx), ptr(iq), ptr(keys), ptr(qpart), ptr(qmax), G,
-                                            ptr(T), min_sigma, alpha, lmbda, weight, ptr(gl), ptr(gQ), ptr(gsig), ptr(gT),
-                                            ptr(dpart), ptr(dloss), _stream(y), deferred_tail, ptr(grad_proj), ptr(grad_sigma)),
+    if state.keys_mode:
+        check(lib.sn_sampler_step_loss_keys(B, N, M, K, ptr(x), BNC, ptr(y), ptr(state.idx), ptr(state.idx_q), ptr(state.keys),
+                                            ptr(state.qpart), ptr(state.qmax), state.G, ptr(T), min_sigma, alpha, lmbda, weight,
+                                            ptr(gl), ptr(gQ), ptr(gsig), ptr(gT), ptr(dpart), ptr(dloss), _stream(y), deferred_tail, ptr(grad_proj), ptr(grad_sigma)),
               "sn_sampler_step_loss_keys")
-        if deferred_tail is not None:
-            # the deferred launch (closing kernel of the conv backward) still reads these: the caller keeps them until then
-            return gQ, gT, (gsig, gl, T)
-        return gQ, gT
+        # the deferred launch (closing kernel of the conv backward) still reads these: the caller keeps them until then
+        return gQ, gT, ((gsig, gl, T) if deferred_tail is not None else None)
     if grad_proj is not None or grad_sigma is not None:
         raise ValueError("step_loss_backward: an explicit grad_proj / grad_sigma needs the keys-mode step")
-    check(lib.sn_sampler_step_loss_backward(B, N, M, K, ptr(x), BNC, ptr(y), ptr(idx), ptr(iq), ptr(ip), ptr(argmax1),
-                                            ptr(T), min_sigma, alpha, lmbda, weight, ptr(gl), ptr(gQ), ptr(gsig), ptr(gT),
-                                            ptr(dpart), ptr(dloss), _stream(y)), "sn_sampler_step_loss_backward")
-    return gQ, gT
+    check(lib.sn_sampler_step_loss_backward(B, N, M, K, ptr(x), BNC, ptr(y), ptr(state.idx), ptr(state.idx_q), ptr(state.idx_p),
+                                            ptr(state.argmax1), ptr(T), min_sigma, alpha, lmbda, weight, ptr(gl), ptr(gQ),
+                                            ptr(gsig), ptr(gT), ptr(dpart), ptr(dloss), _stream(y)), "sn_sampler_step_loss_backward")
+    return gQ, gT, None
 
 
 # --------------------------------------------------------------------------------------------- EMD

@@ -314,11 +314,10 @@ class _Plan:
         self.values = self.outbuf[2 * sec:2 * sec + 8]
         _, proj, state = ops.step_loss_forward(x, self.y, fc, T, K, self.min_sigma, 1.0, 0.0, self.weight, True, keys=self.keys,
                                                proj_out=self.outbuf[sec:sec + B * M * 3].view(B, M, 3))
-        _, keys, qpart, qmax, G = state[5]
         self.dpsum = torch.empty(B, device=self.dev, dtype=torch.float32)
-        check(lib.sn_surface_values_keys(B, N, M, G, ptr(keys), ptr(qpart), ptr(qmax), ptr(T.detach().reshape(1)), self.min_sigma,
-                                         self.weight, ptr(self.y), ptr(self.simp), ptr(self.dpsum), ptr(self.values),
-                                         stream_of(self.x)), "sn_surface_values_keys")
+        check(lib.sn_surface_values_keys(B, N, M, state.G, ptr(state.keys), ptr(state.qpart), ptr(state.qmax),
+                                         ptr(T.detach().reshape(1)), self.min_sigma, self.weight, ptr(self.y), ptr(self.simp),
+                                         ptr(self.dpsum), ptr(self.values), stream_of(self.x)), "sn_surface_values_keys")
         self.saved, self.state, self.proj = saved, state, proj
 
     def _backward_body(self, net):
@@ -327,10 +326,9 @@ class _Plan:
         blob = None
         if pointnet.conv_stack_backward_supported(net, B, N):
             blob = ctypes.create_string_buffer(lib.sn_step_tail_bytes())
-        cfg = (K, self.min_sigma, 1.0, 0.0, self.weight)
-        res = ops.step_loss_backward(self.x, self.y, T, self.state, cfg, self.up_scalars[0:1], self.t_sink, blob, self.up_proj,
-                                     grad_sigma=self.up_scalars[1:2])
-        gQ = res[0]
+        cfg = ops.StepCfg(K, self.min_sigma, 1.0, 0.0, self.weight)
+        gQ, _, keep = ops.step_loss_backward(self.x, self.y, T, self.state, cfg, self.up_scalars[0:1], self.t_sink, blob,
+                                             self.up_proj, grad_sigma=self.up_scalars[1:2])
         if self.with_simp:
             gQ = torch.add(gQ, self.up_simp.permute(0, 2, 1))  # (B,3,M): + the script's own gradient on the simplified cloud
         grads = pointnet.backward_impl(net, self.saved, gQ.view(B, -1), self.views, None, step_tail=blob)
@@ -341,7 +339,7 @@ class _Plan:
             net.project._gate_floor_(self.t_sink)
         if self.collective_in_graph:
             self.reducer._all_reduce_mean(self.reducer.flat)  # captured: RCCL's kernel replays as the graph's last node
-        self.bwd_keep = (res, grads)
+        self.bwd_keep = (keep, grads)
 
     def _capture(self, net, x):
         cur = torch.cuda.current_stream(self.dev)
@@ -542,9 +540,8 @@ class _SurfaceFunction(torch.autograd.Function):
                 gs = g_sigma.reshape(1) if g_sigma is not None else zero
                 gp = g_proj if g_proj is not None else torch.zeros(B, M, 3, device=plan.dev)
                 w = plan.weight if ctx.weight is None else ctx.weight
-                res = ops.step_loss_backward(plan.x, plan.y, T if plan.t_eff is None else plan.t_eff, plan.state,
-                                             (K, plan.min_sigma, 1.0, 0.0, w), gl, None, None, gp, grad_sigma=gs)
-                gQ, gT = res[0], res[1]
+                gQ, gT, _ = ops.step_loss_backward(plan.x, plan.y, T if plan.t_eff is None else plan.t_eff, plan.state,
+                                                   ops.StepCfg(K, plan.min_sigma, 1.0, 0.0, w), gl, None, None, gp, grad_sigma=gs)
                 if plan.t_eff is not None:
                     gT = gT * (T.detach().reshape(gT.shape) >= net.project._temperature_floor).to(gT.dtype)
                 if g_simp is not None:

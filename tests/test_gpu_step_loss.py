@@ -632,3 +632,68 @@ def test_partial_workspace_one_byte_short():
         assert all(g.untouched() for g in o.values())
         rc, o = st.scan_partial(fc=f, ws_bytes=S.partial_ws_bytes(shape))
         assert rc == 0
+
+
+# ================================================================================================ i. the Python hand-off
+HANDOFF_CASES = [((2, 64, 33, 8), "partial"), ((2, 64, 33, 8), "keys"), ((3, 64, 16, 8), "direct"), ((2, 2112, 5, 8), "direct")]
+
+
+@pytest.mark.parametrize("shape,route", HANDOFF_CASES, ids=[_fid(c) for c in HANDOFF_CASES])
+def test_python_hand_off_equals_the_entries(shape, route):
+    """ops.step_loss_forward -> ops.step_loss_backward through the StepLossState record on the smallest row of each route (partial key
+    sets; the keys route on a caller's zeroed table; one workgroup per cloud; N > 2048 with its three-launch backward), the loss value
+    immediate and deferred: proj, the loss, grad_Q and grad_T carry the BITS this file's harness gets from the C entries called directly
+    on the same inputs -- the same kernels with the same arguments, so anything else is a wiring error.  The record's fields are None
+    exactly where the route does not produce them, the key table is zero again behind the keys-mode backward, and without a
+    deferred tail there is nothing to keep."""
+    from samplenet_amd import ops
+
+    B, N, M, K = shape
+    st = Step(shape, "surface")
+    T, ms, alpha, lmbda, weight, g = st.sc
+    cfg = ops.StepCfg(K, ms, alpha, lmbda, weight)
+    assert cfg == (K, ms, alpha, lmbda, weight) and cfg.weight == weight
+    assert (ops.scan_splits(B, N, M) > 1) == (route != "direct") and ops.scan_splits(B, N, M) == max(st.G, 1)
+    for defer in ((True,) if route == "keys" else (False, True)):
+        tag = "%s %s defer=%d " % (S.row_id(shape), route, defer)
+        if route == "keys":
+            rc, e = st.scan_keys()
+            assert rc == 0
+            b = st.keys_backward(e)
+            loss_e = b["loss"]
+        else:
+            if route == "partial":
+                rc, e = st.scan_partial()
+                assert rc == 0
+                st.loss_partial(e, defer)
+            else:
+                e = st.scan_direct()
+                st.loss_direct(e, defer)
+            b = st.backward(e if defer else None)
+            loss_e = e["loss"]
+        keys = torch.zeros(B * N, dtype=torch.int64, device="cuda") if route == "keys" else None
+        loss, proj, state = ops.step_loss_forward(st.dP, st.dQ, None, st.dT, K, ms, alpha, lmbda, weight, defer, keys=keys)
+        gQ, gT, keep = ops.step_loss_backward(st.dP, st.dQ, st.dT, state, cfg, st.dg, None)
+        torch.cuda.synchronize()
+        _same_bits(tag + "proj", proj.cpu().numpy(), e["proj"].numpy())
+        _same_bits(tag + "loss", loss.cpu().numpy(), loss_e.check("loss").cpu().numpy())
+        _same_bits(tag + "grad_Q", gQ.cpu().numpy(), b["gQ"].numpy())
+        _same_bits(tag + "grad_T", gT.cpu().numpy(), b["gT"].check("grad_T").cpu().numpy())
+        assert keep is None
+        _same_bits(tag + "state.idx", state.idx.cpu().numpy(), e["knn"].numpy())
+        _same_bits(tag + "state.idx_q", state.idx_q.cpu().numpy(), e["iq"].numpy())
+        if route == "keys":
+            assert state.keys_mode and state.keys is keys and state.G == st.G
+            assert state.idx_p is None and state.argmax1 is None
+            assert state.qpart.shape == (B * st.G * 2,) and state.qmax.shape == (B * st.G,)
+            assert state.deferred[0] is not None and state.deferred[1] is loss
+            assert not keys.any().item(), "the key table is not zero again"
+        else:
+            assert not state.keys_mode
+            assert state.keys is None and state.qpart is None and state.qmax is None and state.G is None
+            _same_bits(tag + "state.idx_p", state.idx_p.cpu().numpy(), e["ip"].numpy())
+            _same_bits(tag + "state.argmax1", state.argmax1.cpu().numpy(), e["am"].numpy())
+            if defer:
+                assert state.deferred[0] is not None and state.deferred[1] is loss
+            else:
+                assert state.deferred == (None, None)

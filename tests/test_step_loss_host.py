@@ -43,6 +43,29 @@ def test_every_row_has_the_splits_the_library_answers(lib):
     assert lib.sn_pairscan_colmin_splits(0, 8, 8) == 0 and lib.sn_pairscan_colmin_splits(2, 0, 8) == 0 and lib.sn_pairscan_colmin_splits(2, 8, -1) == 0
 
 
+def test_route_functions_answer_the_table(lib):
+    """ops.scan_splits / ops.keys_step_possible, which every Python caller of the chain decides its route by: the table's G on every
+    row, the keys-mode step exactly on the split rows (all of them N <= 2048; (2, 2112, 5, 8) stands on the other side of that
+    bound), and on none with the test hook off."""
+    from samplenet_amd import fused_step, ops
+
+    assert any(s[1] > 2048 for s in S.DIRECT) and all(s[1] <= 2048 for s in S.SPLIT)
+    for shape, G, why in S.SPLIT_ROWS:
+        B, N, M, K = shape
+        assert ops.scan_splits(B, N, M) == G, (shape, why)
+        assert ops.keys_step_possible(B, N, M) is True, (shape, why)
+    for shape, why in S.DIRECT_ROWS:
+        B, N, M, K = shape
+        assert ops.scan_splits(B, N, M) == 1, (shape, why)
+        assert ops.keys_step_possible(B, N, M) is False, (shape, why)
+    old = fused_step.KEYS_LOSS
+    try:
+        fused_step.KEYS_LOSS = False
+        assert not any(ops.keys_step_possible(*s[:3]) for s in S.ROWS)
+    finally:
+        fused_step.KEYS_LOSS = old
+
+
 def test_rows_reach_the_branches_they_are_named_for():
     plan = {s: S.scan_plan(*s[:3]) for s in S.ROWS}
     B, N, M, K = S.NO_QUERY_ROW
