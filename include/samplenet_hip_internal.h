@@ -465,6 +465,22 @@ int sn_classification_terms_backward(int B, int C, const float *logits, const in
  * `out` bits as sn_nn_matching. */
 int sn_nn_matching_indexed(int B, int N, int k, const float *xyz, int layout, const int *idx, int complete_fps, float *out,
                            int *out_idx, int *n_unique, sn_stream_t stream);
+/* A whole cloud ranked by importance: the progressive sampler's inference (classification/infer_samplenet_progressive.py:207-212,
+ * reconstruction/src/samplenet_progressive_pointnet_ae.py:490-524).
+ * idx (B,k): nearest input point of every generated point, in generation order.  out_idx (B,k): the distinct values of
+ * idx[b,:] in order of first occurrence, then farthest-point picks up to k -- fps_from_given_indices
+ * (samplenet_progressive_pointnet_ae.py:567-585): float64 ((dx*dx + dy*dy) + dz*dz) never contracted, np.argmax's first
+ * maximum (ties to the lowest point index).  out (B,k,3) = xyz[out_idx]; n_unique (B,) = number of distinct values.
+ * out / out_idx / n_unique may each be NULL.  1 <= N <= 8192, 1 <= k <= 8192 (k may exceed N: once every distinct point
+ * is taken all distances are 0 and index 0 comes again, as in numpy).  idx values are clamped into [0,N): no input makes
+ * the kernel read outside xyz.  temp: sn_workspace_bytes("rank_points", B, N, k, 0) bytes, may be 0 / NULL (it is 0 today: a
+ * cloud's state lives in its workgroup's LDS).  Where sn_nn_matching_indexed(complete_fps = 1) accepts the shape (k <= 1024) the three
+ * outputs are bit-identical to its. */
+int sn_rank_points(int B, int N, int k, const float *xyz, int layout, const int *idx, float *temp, float *out, int *out_idx,
+                   int *n_unique, sn_stream_t stream);
+/* measurement hook: points per lane (1, 2, 4, 8; 0 = chosen by N) of every later sn_rank_points call; returns the previous value,
+ * -1 for a bad one.  A value that cannot hold N in 1024 lanes makes the call SN_ERR_UNSUPPORTED.  Outputs do not depend on it. */
+int sn_rank_points_set_ppt(int ppt);
 
 /* The progressive sampler's nested prefixes (classification/train_samplenet_progressive.py:157-234) as contiguous tensors in ONE launch:
  * src (B, M, C) of 4-byte elements -> dst[j] (B, sizes[j], C) = src[:, :sizes[j], :] (dst: HOST array of nprefix <= 16 device

@@ -14,7 +14,8 @@ from .chamfer_distance import ChamferDistance, ChamferDistanceFunction  # noqa: 
 from .qtransform import QuaternionTransform, deg_to_rad, qinv, rad_to_deg  # noqa: F401
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
-from .evaluation import (ClassificationEvaluator, ReconstructionEvaluator, RegistrationEvaluator,  # noqa: F401
+from .evaluation import (ClassificationEvaluator, ProgressiveClassificationEvaluator,  # noqa: F401
+                         ProgressiveReconstructionEvaluator, ReconstructionEvaluator, RegistrationEvaluator,
                          classification_aggregates)
 from .samplers import FPSSampler, RandomSampler  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
@@ -23,4 +24,4 @@ __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "Samp
            "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
            "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet", "QuaternionTransform", "qinv", "rad_to_deg",
            "deg_to_rad", "RegistrationEvaluator", "ClassificationEvaluator", "ReconstructionEvaluator",
-           "classification_aggregates"]
+           "ProgressiveClassificationEvaluator", "ProgressiveReconstructionEvaluator", "classification_aggregates"]

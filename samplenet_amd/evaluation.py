@@ -2,7 +2,10 @@
 (RegistrationEvaluator, below first); classification: `classification/evaluate_samplenet.py:156-277` (ClassificationEvaluator);
 reconstruction: `reconstruction/sampler/evaluate_samplenet.py:88-152` with `get_loss_ae_per_pc` of
 `reconstruction/src/sampler_autoencoder.py:149-167` (ReconstructionEvaluator).  All three keep every value per cloud on the device,
-never synchronise in `add`, and make one transfer in `result`.
+never synchronise in `add`, and make one transfer in `result`.  The progressive sampler's evaluation -- the cloud ranked once, the
+task network run on every prefix (`classification/infer_samplenet_progressive.py:114,207-212` + `evaluate_samplenet.py`,
+`reconstruction/sampler/evaluate_samplenet_progressive.py:105-141`) -- is ProgressiveClassificationEvaluator /
+ProgressiveReconstructionEvaluator at the end, over the same per-batch steps and aggregates.
 
 The reference tests at batch_size 1 with an `.item()` per cloud and metric (main.py:128, 444-450).  Here a batch of any size goes
 through the same steps -- sampling, PCRNet, the pose-error terms, the Chamfer term, the sampling consistency -- with every value
@@ -166,6 +169,21 @@ def classification_aggregates(preds, labels, batch_sizes, batch_losses, n_unique
             "mean_unique": float(np.sum(np.asarray(n_unique, dtype=np.float64))) / float(total_seen)}
 
 
+def _classify_batch(classifier, cloud, labels, reg_weight):
+    """One batch of one cloud size through the classifier: -> (logits, (3,B) rows pred / label / cross-entropy, loss_val (1,)) with
+    loss_val = the batch's mean cross-entropy plus the weighted orthogonality term (evaluate_samplenet.py:236-241)."""
+    from .classifier import orthogonality_loss
+
+    logits, end_points = classifier(_to_shape(cloud, classifier))
+    ce, pred, _correct, means = ops.classification_terms(logits, labels)
+    loss_val = means[0]
+    t = end_points.get("transform")
+    if t is not None:
+        loss_val = loss_val + reg_weight * orthogonality_loss(t)
+    # (class indices and counts are far below 2^24: exact as float32)
+    return logits, torch.stack([pred.float(), labels.float(), ce]), loss_val.reshape(1)
+
+
 class ClassificationEvaluator:
     """classifier: a PointNetCls / PointNetClsBasic; sampler: a SampleNet (sample_indices: the inference branch with its indices),
     an FPSSampler / RandomSampler, or None (the whole cloud); match_output: classify the matched cloud, else the simplified one
@@ -182,24 +200,16 @@ class ClassificationEvaluator:
 
     def add(self, x, labels):
         """One batch: x (B,N,3) and labels (B,) integer class indices on the GPU.  No synchronisation."""
-        from .classifier import orthogonality_loss
-
         if not (x.is_cuda and labels.is_cuda):
             raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
         with _EvalMode(self.classifier, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             simp, match, _idx, nun = _sample_with_indices(self.sampler, x)
             cloud = match if self.match_output else simp
-            logits, end_points = self.classifier(_to_shape(cloud, self.classifier))
-            ce, pred, _correct, means = ops.classification_terms(logits, labels)
-            loss_val = means[0]
-            t = end_points.get("transform")
-            if t is not None:
-                loss_val = loss_val + self.reg_weight * orthogonality_loss(t)
-            # (class indices and counts are far below 2^24: exact as float32)
-            self._rows.append(torch.stack([pred.float(), labels.float(), ce, nun.float()]))
+            logits, rows, loss_val = _classify_batch(self.classifier, cloud, labels, self.reg_weight)
+            self._rows.append(torch.cat([rows, nun.float().unsqueeze(0)]))
             self._sizes.append(int(x.shape[0]))
-            self._losses.append(loss_val.reshape(1))
+            self._losses.append(loss_val)
             if self.keep:
                 self._logits.append(logits.reshape(-1))
                 self._clouds.append(cloud.reshape(-1))
@@ -228,6 +238,18 @@ class ClassificationEvaluator:
 
 
 # ------------------------------------------------------------------------------------------------ reconstruction
+def reconstruction_aggregates(losses, reference_losses=None):
+    """losses, mean_loss and, with the autoencoder's losses on the complete clouds, reference_losses, nre (their quotient, np.divide as
+    the reference), mean_reference_loss, mean_nre (evaluate_samplenet.py:143, 151-152) from per-item float64 arrays."""
+    out = {"losses": losses, "mean_loss": float(losses.mean())}
+    if reference_losses is not None:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nre = np.divide(losses, reference_losses)
+        out.update(reference_losses=reference_losses, nre=nre, mean_reference_loss=float(reference_losses.mean()),
+                   mean_nre=float(nre.mean()))
+    return out
+
+
 class ReconstructionEvaluator:
     """autoencoder: a PointNetAE; sampler as ClassificationEvaluator's (the matched points are reconstructed from); loss "chamfer"
     (ops.chamfer_mean_per_cloud) or "emd" (ops.emd_loss' per-cloud costs): get_loss_ae_per_pc (sampler_autoencoder.py:149-167: the
@@ -279,12 +301,8 @@ class ReconstructionEvaluator:
             parts += [kept[k] for kept in self._kept]
         flat = torch.cat(parts).cpu().numpy()
         table = flat[:3 * n].reshape(3, n).astype(np.float64)
-        out = {"losses": table[0], "n_unique": table[2].astype(np.int64), "mean_loss": float(table[0].mean()),
-               "mean_unique": float(table[2].mean())}
-        if self.with_reference:
-            with np.errstate(invalid="ignore", divide="ignore"):
-                nre = np.divide(table[0], table[1])
-            out.update(reference_losses=table[1], nre=nre, mean_reference_loss=float(table[1].mean()), mean_nre=float(nre.mean()))
+        out = {"n_unique": table[2].astype(np.int64), "mean_unique": float(table[2].mean())}
+        out.update(reconstruction_aggregates(table[0], table[1] if self.with_reference else None))
         if self.keep:
             M, R = self._shape
             o = 3 * n
@@ -293,4 +311,192 @@ class ReconstructionEvaluator:
             out["sample_idx"] = flat[o:o + n * M].astype(np.int64).reshape(n, M)
             o += n * M
             out["reconstructions"] = flat[o:o + n * R * 3].reshape(n, R, 3).copy()
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ progressive sampling
+def _ranked_cloud(sampler, x, size):
+    """x (B,N,3) -> (ordered (B,size,3), order (B,size) int32, n_unique (B,) int32): the first `size` points of the cloud in the
+    sampler's order of importance.  A module with `rank` (SampleNetProgressive): its ranking, n_unique the distinct nearest
+    neighbours before completion; an FPSSampler: the farthest-point order of `size` points (honouring its `permute`) -- a prefix
+    of a farthest-point order is the farthest-point sample of that size; None: the input order.  For the latter two n_unique is
+    `size`, the number of points taken."""
+    from .samplers import FPSSampler
+
+    B, N, _ = x.shape
+    if sampler is None or isinstance(sampler, FPSSampler):
+        if size > N:
+            raise ValueError("the largest size (%d) exceeds the cloud's %d points" % (size, N))
+        nun = torch.full((B,), size, device=x.device, dtype=torch.int32)
+        if sampler is None:
+            order = torch.arange(size, device=x.device, dtype=torch.int32).expand(B, size).contiguous()
+            return x[:, :size].contiguous(), order, nun
+        # (one randperm on the default device, as the sampler draws it; sent from pinned memory, so that add() does not synchronise)
+        perm = torch.randperm(N).pin_memory().to(x.device, non_blocking=True) if sampler.permute else None
+        src = x[:, perm, :].contiguous() if perm is not None else x
+        order = ops.furthest_point_sample(src, size, ops.BNC)
+        ordered = ops.group_point(src, order.unsqueeze(-1)).squeeze(2).contiguous()
+        return ordered, (perm.int()[order.long()] if perm is not None else order), nun
+    if not hasattr(sampler, "rank"):
+        raise TypeError("sampler: a module with rank() (SampleNetProgressive), an FPSSampler or None")
+    xin = x if sampler.input_shape == "bnc" else x.permute(0, 2, 1).contiguous()
+    ordered, order, nun = sampler.rank(xin)
+    if sampler.output_shape != "bnc":
+        ordered = ordered.permute(0, 2, 1)
+    if ordered.shape[1] < size:
+        raise ValueError("the largest size (%d) exceeds the %d points the sampler ranks" % (size, ordered.shape[1]))
+    return ordered[:, :size].contiguous(), order[:, :size].contiguous(), nun
+
+
+def _default_sizes(sampler, sizes):
+    if sizes is None:
+        sizes = getattr(sampler, "sizes", None)
+        if sizes is None and getattr(sampler, "num_out_points", None) is not None:
+            sizes = [sampler.num_out_points]
+    if sizes is None:
+        raise ValueError("sizes: needed when the sampler has none of its own")
+    sizes = sorted(int(s) for s in sizes)
+    if not sizes or sizes[0] < 1 or len(set(sizes)) != len(sizes):
+        raise ValueError("sizes must be distinct positive integers")
+    return sizes
+
+
+class ProgressiveClassificationEvaluator:
+    """The classifier's figures at EVERY sample size from one ranking per batch (infer_samplenet_progressive.py:207-212 feeding
+    evaluate_samplenet.py:156-277 once per size).  classifier, reg_weight, keep: as ClassificationEvaluator; sampler: a module with
+    `rank` (SampleNetProgressive), an FPSSampler (the baseline curve) or None (the input order); sizes: default the sampler's.
+    Clouds are (B,N,3)."""
+
+    def __init__(self, classifier, sampler, sizes=None, reg_weight=0.001, keep=False):
+        self.classifier, self.sampler = classifier, sampler
+        self.sizes = _default_sizes(sampler, sizes)
+        self.reg_weight, self.keep = float(reg_weight), bool(keep)
+        self.reset()
+
+    def reset(self):
+        self._rows = {s: [] for s in self.sizes}    # (3, B): pred, label, cross-entropy
+        self._losses = {s: [] for s in self.sizes}
+        self._logits = {s: [] for s in self.sizes}
+        self._unique, self._batch, self._ranked = [], [], []
+
+    def add(self, x, labels):
+        """One batch: x (B,N,3) and labels (B,) on the GPU: ranked once, classified once per size.  No synchronisation."""
+        if not (x.is_cuda and labels.is_cuda):
+            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        with _EvalMode(self.classifier, self.sampler), torch.no_grad():
+            x = x.contiguous().float()
+            ordered, order, nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
+            for s in self.sizes:
+                logits, rows, loss_val = _classify_batch(self.classifier, ordered[:, :s].contiguous(), labels, self.reg_weight)
+                self._rows[s].append(rows)
+                self._losses[s].append(loss_val)
+                if self.keep:
+                    self._logits[s].append(logits.reshape(-1))
+                self._num_classes = int(logits.shape[1])
+            self._unique.append(nun.float())
+            self._batch.append(int(x.shape[0]))
+            if self.keep:
+                self._ranked.append((ordered.reshape(-1), order.float().reshape(-1)))  # (indices are below 2^24: exact)
+
+    def result(self):
+        """One device-to-host transfer -> {"sizes", "n_unique" (items,) int64, "mean_unique", "by_size": {s: ...}}: by_size[s] holds
+        what ClassificationEvaluator.result() holds for the first s ranked points (preds, labels, losses, batch_sizes, batch_losses,
+        classification_aggregates of them) except the unique counts, which belong to the ranking; with keep=True by_size[s]["logits"]
+        and, at the top, "ordered" (items, max size, 3) and "order" (items, max size) int64."""
+        if not self._batch:
+            raise RuntimeError("ProgressiveClassificationEvaluator.result: nothing was added")
+        n, nb, C, M = sum(self._batch), len(self._batch), self._num_classes, self.sizes[-1]
+        parts = [torch.cat(self._unique)]
+        for s in self.sizes:
+            parts += [torch.cat(self._rows[s], dim=1).reshape(-1)] + self._losses[s] + self._logits[s]
+        for k in range(2):
+            parts += [r[k] for r in self._ranked]
+        flat = torch.cat(parts).cpu().numpy()
+        n_unique, o = flat[:n].astype(np.int64), n
+        batch_sizes = np.asarray(self._batch, dtype=np.int64)
+        out = {"sizes": list(self.sizes), "n_unique": n_unique, "by_size": {}}
+        for s in self.sizes:
+            table = flat[o:o + 3 * n].reshape(3, n).astype(np.float64)
+            o += 3 * n
+            r = {"preds": table[0].astype(np.int64), "labels": table[1].astype(np.int64), "losses": table[2],
+                 "batch_sizes": batch_sizes, "batch_losses": flat[o:o + nb].astype(np.float64)}
+            o += nb
+            if self.keep:
+                r["logits"] = flat[o:o + n * C].reshape(n, C).copy()
+                o += n * C
+            r.update(classification_aggregates(r["preds"], r["labels"], batch_sizes, r["batch_losses"], n_unique, C))
+            out["mean_unique"] = r.pop("mean_unique")  # (the ranking's, the same at every size)
+            out["by_size"][s] = r
+        if self.keep:
+            out["ordered"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
+            out["order"] = flat[o + n * M * 3:o + n * M * 4].astype(np.int64).reshape(n, M)
+        return out
+
+
+class ProgressiveReconstructionEvaluator:
+    """The autoencoder's per-cloud loss at EVERY sample size from one ranking per batch (evaluate_samplenet_progressive.py:105-141).
+    autoencoder, loss, with_reference, keep: as ReconstructionEvaluator -- the reference loss (the autoencoder on the complete cloud)
+    is computed once per batch, the nre per size; sampler, sizes: as ProgressiveClassificationEvaluator.  Clouds are (B,N,3)."""
+
+    def __init__(self, autoencoder, sampler, sizes=None, loss="chamfer", with_reference=True, keep=False):
+        if loss not in ("chamfer", "emd"):
+            raise ValueError("loss: 'chamfer' or 'emd'")
+        self.autoencoder, self.sampler = autoencoder, sampler
+        self.sizes = _default_sizes(sampler, sizes)
+        self.loss, self.with_reference, self.keep = loss, bool(with_reference), bool(keep)
+        self.reset()
+
+    def reset(self):
+        self._losses = {s: [] for s in self.sizes}
+        self._recons = {s: [] for s in self.sizes}
+        self._shared, self._batch, self._ranked = [], [], []  # _shared: (2, B) reference loss, n_unique
+
+    _per_cloud = ReconstructionEvaluator._per_cloud
+
+    def add(self, x):
+        """One batch: x (B,N,3) on the GPU: ranked once, reconstructed once per size.  No synchronisation."""
+        if not x.is_cuda:
+            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ae = self.autoencoder
+        with _EvalMode(ae, self.sampler), torch.no_grad():
+            x = x.contiguous().float()
+            ordered, order, nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
+            for s in self.sizes:
+                recon = ae(_to_shape(ordered[:, :s].contiguous(), ae)).contiguous()
+                self._losses[s].append(self._per_cloud(recon, x))
+                if self.keep:
+                    self._recons[s].append(recon.reshape(-1))
+                self._recon_points = int(recon.shape[1])
+            ref = self._per_cloud(ae(_to_shape(x, ae)).contiguous(), x) if self.with_reference else torch.zeros_like(nun, dtype=torch.float32)
+            self._shared.append(torch.stack([ref, nun.float()]))
+            self._batch.append(int(x.shape[0]))
+            if self.keep:
+                self._ranked.append((ordered.reshape(-1), order.float().reshape(-1)))
+
+    def result(self):
+        """One device-to-host transfer -> {"sizes", "n_unique", "mean_unique", "by_size": {s: reconstruction_aggregates (losses,
+        mean_loss and, with_reference, reference_losses -- the same array at every size --, nre, mean_reference_loss, mean_nre)}};
+        with keep=True by_size[s]["reconstructions"] and, at the top, "ordered" and "order" (int64)."""
+        if not self._batch:
+            raise RuntimeError("ProgressiveReconstructionEvaluator.result: nothing was added")
+        n, M = sum(self._batch), self.sizes[-1]
+        parts = [torch.cat(self._shared, dim=1).reshape(-1)]
+        for s in self.sizes:
+            parts += self._losses[s] + self._recons[s]
+        for k in range(2):
+            parts += [r[k] for r in self._ranked]
+        flat = torch.cat(parts).cpu().numpy()
+        shared, o = flat[:2 * n].reshape(2, n).astype(np.float64), 2 * n
+        out = {"sizes": list(self.sizes), "n_unique": shared[1].astype(np.int64), "mean_unique": float(shared[1].mean()), "by_size": {}}
+        for s in self.sizes:
+            r = reconstruction_aggregates(flat[o:o + n].astype(np.float64), shared[0] if self.with_reference else None)
+            o += n
+            if self.keep:
+                R = self._recon_points
+                r["reconstructions"] = flat[o:o + n * R * 3].reshape(n, R, 3).copy()
+                o += n * R * 3
+            out["by_size"][s] = r
+        if self.keep:
+            out["ordered"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
+            out["order"] = flat[o + n * M * 3:o + n * M * 4].astype(np.int64).reshape(n, M)
         return out

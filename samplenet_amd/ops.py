@@ -356,6 +356,31 @@ def nn_matching_indexed(xyz, idx, k, complete_fps=True, layout=BNC):
     return out, out_idx, n_unique
 
 
+def rank_points(xyz, idx, k=None, layout=BNC):
+    """A whole cloud re-ordered by importance (the progressive sampler's inference, samplenet_progressive_pointnet_ae.py:490-524,
+    546-600): xyz (B,N,3) [BNC] or (B,3,N) [BCN], idx (B,k) nearest input point of every generated point in generation order ->
+    (points (B,k,3) float32, order (B,k) int32, n_unique (B,) int32).  order: the distinct values of idx in order of first
+    occurrence, then farthest-point picks up to k (float64 distances, first maximum); points = xyz[order]; n_unique: the distinct
+    values of idx[b, :].  k defaults to idx's width; N, k <= 8192 (sn_rank_points); every prefix order[:, :s] is the sample of
+    size s.  One launch, no synchronisation, no gradient."""
+    _need_gpu(xyz, idx)
+    xyz = _f32c(xyz.detach())
+    idx = idx.detach().reshape(idx.shape[0], -1).contiguous().int()
+    B = xyz.shape[0]
+    N = xyz.shape[1] if layout == BNC else xyz.shape[2]
+    if k is None:
+        k = idx.shape[1]
+    if idx.shape[1] != k:
+        raise ValueError("rank_points: idx must hold k indices per cloud")
+    out = torch.empty(B, k, 3, device=xyz.device, dtype=torch.float32)
+    order = torch.empty(B, k, device=xyz.device, dtype=torch.int32)
+    n_unique = torch.empty(B, device=xyz.device, dtype=torch.int32)
+    with torch.cuda.device(xyz.device):
+        check(lib.sn_rank_points(B, N, k, ptr(xyz), layout, ptr(idx), None, ptr(out), ptr(order), ptr(n_unique), _stream(xyz)),
+              "sn_rank_points")
+    return out, order, n_unique
+
+
 def furthest_point_sample(xyz, npoint, layout=BNC):
     """Farthest-point sampling (no gradient): xyz (B,N,3) [BNC] or (B,3,N) [BCN] -> idx (B,npoint) int32.
 

@@ -33,6 +33,9 @@ class SampleNetProgressive(SampleNet):
     """SampleNet(num_out_points = the largest size) + prefix-wise losses.
 
     forward(x) -> (simp, proj) exactly as SampleNet; slice both with [:, :s] (output_shape 'bnc') for the task network.
+    Inference: rank(x) -> (ordered, order, n_unique) (SampleNet.rank: the reference's get_sample(X, complete_fps=True)) -- the input
+    cloud re-ordered by importance on the device, every sample size a prefix of it; evaluation.ProgressiveClassificationEvaluator /
+    ProgressiveReconstructionEvaluator evaluate the task network on every prefix of one ranking.
     """
 
     def __init__(self, sizes, bottleneck_size, group_size, **kw):

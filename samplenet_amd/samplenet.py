@@ -231,6 +231,32 @@ class SampleNet(nn.Module):
             self.train(was)
         return simp, match, out_idx, n_unique
 
+    def rank(self, x):
+        """The input cloud re-ordered by importance -- the progressive sampler's get_sample(X, complete_fps=True)
+        (samplenet_progressive_pointnet_ae.py:490-509, infer_samplenet_progressive.py:207-212): x in `input_shape` -> (ordered in
+        `output_shape`: the num_out_points matched points, first the distinct nearest neighbours of the generated points in
+        generation order, then farthest-point picks; order (B,M) int32: their indices in x; n_unique (B,) int32).  Every sample
+        size is a prefix.  As sample_indices: whatever the module's mode (left as found), eval-mode BatchNorm, no gradient; two
+        launches behind the head (ops.knn(1), ops.rank_points) and no host round trip up to 8192 points."""
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                cloud_is_bnc = self.input_shape == "bnc"
+                x_bcn = x.permute(0, 2, 1) if cloud_is_bnc else x
+                if x_bcn.shape[1] != 3:
+                    raise RuntimeError("shape of x must be of [Batch x 3 x NumInPoints]")
+                y = self._features(x_bcn, x if cloud_is_bnc else None)  # (B,3,M)
+                cloud = (x if cloud_is_bnc else x_bcn).contiguous()
+                layout = ops.BNC if cloud_is_bnc else ops.BCN
+                idx, _ = ops.knn(1, cloud, y.contiguous(), layout, ops.BCN, return_dist=False)  # (B,M,1)
+                ordered, order, n_unique = ops.rank_points(cloud, idx, self.num_out_points, layout)
+                if self.output_shape != "bnc":
+                    ordered = ordered.permute(0, 2, 1).contiguous()
+        finally:
+            self.train(was)
+        return ordered, order, n_unique
+
     def check(self):
         """Host-side health check of the FC chain launches' hand-off state (pointnet.check_chain_errors): raises
         SampleNetHipError when a step since the last check ran on incomplete data (its outputs / gradients were NaN-poisoned on
