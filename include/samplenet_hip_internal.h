@@ -482,6 +482,26 @@ int sn_rank_points(int B, int N, int k, const float *xyz, int layout, const int 
  * -1 for a bad one.  A value that cannot hold N in 1024 lanes makes the call SN_ERR_UNSUPPORTED.  Outputs do not depend on it. */
 int sn_rank_points_set_ppt(int ppt);
 
+/* All-against-all shape retrieval inside one labelled set (the sampler's fourth application, README.md:13, on the classifier's
+ * end_points["retrieval_vectors"], classification/models/pointnet_cls.py:111; the reference has no script for it, so this text is
+ * the contract, restated in numpy by tests/retrieval_ref.py).  desc (S,n,C) fp32: S descriptor sets over the same n shapes (one per
+ * sample size for a progressive sampler); labels (n) int32.  Every shape is a query against the other n - 1:
+ *   d(i,j)  = sum_c (a_ic - a_jc)^2 in fp32, from the differences, nothing contracted, in one fixed order: the channels
+ *             c = l, l + 64, l + 128, .. are added in ascending order for every l < 64, then the 64 partial sums meet as a balanced
+ *             tree of adjacent pairs.  d(i,j) == d(j,i) bit for bit; equal descriptors give exactly +0;
+ *   ranking = all j != i ascending by (d(i,j), j): ties to the lower index (numpy's stable argsort without the query);
+ *   R = the others with the query's label, H(r) = those among the first r ranks;
+ *   ap      = (sum over the relevant ranks r of H(r) / r) / R, accumulated in fp64, rounded once to fp32;
+ *   prec[l-1], l = 1..L: H(r) / r (one fp64 division, rounded to fp32) at the smallest r with H(r) >= (l R + L - 1) / L (integer
+ *             division: ceil(l R / L)): the precision at recall l / L;
+ *   R == 0 (n == 1 included): ap and prec are NaN and n_relevant is 0.
+ * Outputs (caller-owned, each may be NULL): ap (S,n), prec (S,n,L), n_relevant (n), order (S,n,n-1) int32, sorted_dist (S,n,n-1).
+ * workspace: sn_workspace_bytes("retrieval_metrics", S, n, C, L) bytes, may be 0 / NULL (it is 0 today: a query's keys live in its
+ * workgroup's LDS).  One launch, stream-ordered, capturable.  S == 0 or n == 0 is a no-op.  C < 1, L < 1, a negative size or a NULL
+ * desc (NULL labels with ap / prec / n_relevant wanted) -> SN_ERR_BAD_ARGUMENT; n > 8192, L > 64 or S > 65535 -> SN_ERR_UNSUPPORTED. */
+int sn_retrieval_metrics(int S, int n, int C, const float *desc, const int *labels, int L, float *ap, float *prec, int *n_relevant,
+                         int *order, float *sorted_dist, void *workspace, sn_stream_t stream);
+
 /* The progressive sampler's nested prefixes (classification/train_samplenet_progressive.py:157-234) as contiguous tensors in ONE launch:
  * src (B, M, C) of 4-byte elements -> dst[j] (B, sizes[j], C) = src[:, :sizes[j], :] (dst: HOST array of nprefix <= 16 device
  * pointers, NULL entries skipped); and the gradient of that in one launch: out (B, M, C) = sum over j of grads[j] zero-padded to

@@ -15,8 +15,8 @@ from .qtransform import QuaternionTransform, deg_to_rad, qinv, rad_to_deg  # noq
 from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
 from .evaluation import (ClassificationEvaluator, ProgressiveClassificationEvaluator,  # noqa: F401
-                         ProgressiveReconstructionEvaluator, ReconstructionEvaluator, RegistrationEvaluator,
-                         classification_aggregates)
+                         ProgressiveReconstructionEvaluator, ProgressiveRetrievalEvaluator, ReconstructionEvaluator,
+                         RegistrationEvaluator, RetrievalEvaluator, classification_aggregates, retrieval_aggregates)
 from .samplers import FPSSampler, RandomSampler  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
 
@@ -24,4 +24,5 @@ __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "Samp
            "progressive_sizes", "PointNetAE", "reconstruction_loss", "PointNetCls", "PointNetClsBasic", "classification_loss",
            "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet", "QuaternionTransform", "qinv", "rad_to_deg",
            "deg_to_rad", "RegistrationEvaluator", "ClassificationEvaluator", "ReconstructionEvaluator",
-           "ProgressiveClassificationEvaluator", "ProgressiveReconstructionEvaluator", "classification_aggregates"]
+           "ProgressiveClassificationEvaluator", "ProgressiveReconstructionEvaluator", "classification_aggregates",
+           "RetrievalEvaluator", "ProgressiveRetrievalEvaluator", "retrieval_aggregates"]

@@ -174,6 +174,7 @@ PROTOTYPES = {
     "sn_nn_matching_indexed": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "sn_rank_points": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_rank_points_set_ppt": [_i],
+    "sn_retrieval_metrics": [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_batch_state_bytes": [],
     "sn_batch_assemble": [_i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _i, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp,
                           _vp, _vp, _vp, _vp],

@@ -26,6 +26,8 @@ SOURCES = [
     ("sampling.hip", ["-ffp-contract=off"]),
     # the ranking's fp64 distance is numpy's: product then sum, one rounding per operation (tests/rank_ref.py)
     ("rank_points.hip", ["-ffp-contract=off"]),
+    # the retrieval distance is difference, product, sum in one written-out order (tests/retrieval_ref.py restates it in fp32)
+    ("retrieval.hip", ["-ffp-contract=off"]),
     # emd.hip carries HAND-WRITTEN packed fp32 instructions (inline asm, destination pair disjoint from every source: the form a
     # replayed instruction cannot get wrong) -- the assembler needs the feature, the compiler's own packing stays off through
     # the SLP vectoriser switch; tests/test_cabi_and_host.py checks the disassembly for both properties

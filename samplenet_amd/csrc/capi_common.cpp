@@ -34,6 +34,8 @@ extern "C" long long sn_workspace_bytes(const char *op, int B, int N, int M, int
         return sn_emd_loss_floats(B, N, M) * 4;
     // furthest_point_sample: the streaming path's running minima (B*N floats); 0 where the shape runs register-resident
     if (!strcmp(op, "furthest_point_sample")) return B > 0 && N > 0 && sn::fps_choose(B, N) == 3 ? (long long)B * N * 4 : 0;
+    // retrieval_metrics (S, n, C, L): a query's keys are sorted in its workgroup's LDS
+    if (!strcmp(op, "retrieval_metrics")) return 0;
     return 0;
 }
 

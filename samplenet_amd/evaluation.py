@@ -5,7 +5,9 @@ reconstruction: `reconstruction/sampler/evaluate_samplenet.py:88-152` with `get_
 never synchronise in `add`, and make one transfer in `result`.  The progressive sampler's evaluation -- the cloud ranked once, the
 task network run on every prefix (`classification/infer_samplenet_progressive.py:114,207-212` + `evaluate_samplenet.py`,
 `reconstruction/sampler/evaluate_samplenet_progressive.py:105-141`) -- is ProgressiveClassificationEvaluator /
-ProgressiveReconstructionEvaluator at the end, over the same per-batch steps and aggregates.
+ProgressiveReconstructionEvaluator, over the same per-batch steps and aggregates.  Retrieval, the fourth application the reference
+names (README.md:13) without a script for it, closes the file: RetrievalEvaluator / ProgressiveRetrievalEvaluator collect the
+classifier's descriptors and rank and score all of them against each other in one launch (ops.retrieval_metrics).
 
 The reference tests at batch_size 1 with an `.item()` per cloud and metric (main.py:128, 444-450).  Here a batch of any size goes
 through the same steps -- sampling, PCRNet, the pose-error terms, the Chamfer term, the sampling consistency -- with every value
@@ -499,4 +501,121 @@ class ProgressiveReconstructionEvaluator:
         if self.keep:
             out["ordered"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
             out["order"] = flat[o + n * M * 3:o + n * M * 4].astype(np.int64).reshape(n, M)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ retrieval
+def retrieval_aggregates(ap, prec, n_relevant):
+    """The figures of a retrieval experiment from the per-query arrays of ops.retrieval_metrics, in float64: ap (n,), prec (n, L),
+    n_relevant (n,).  A query is valid when another shape carries its label (n_relevant > 0; its ap and prec are NaN otherwise) and
+    only valid queries enter a mean: map = mean ap, pr_curve (L,) = mean precision at recall l / L, auc = mean of pr_curve (the
+    normalised area on that recall grid), n_valid.  No valid query: NaN everywhere, n_valid 0."""
+    ap, prec = np.asarray(ap, dtype=np.float64), np.asarray(prec, dtype=np.float64)
+    valid = np.asarray(n_relevant) > 0
+    n_valid = int(valid.sum())
+    if n_valid == 0:
+        curve = np.full(prec.shape[1], np.nan)
+        return {"map": float("nan"), "pr_curve": curve, "auc": float("nan"), "n_valid": 0}
+    curve = prec[valid].sum(axis=0) / n_valid
+    return {"map": float(ap[valid].sum() / n_valid), "pr_curve": curve, "auc": float(curve.sum() / len(curve)), "n_valid": n_valid}
+
+
+def _descriptors(classifier, cloud):
+    """one batch of one cloud size through the classifier: its shape descriptor, end_points["retrieval_vectors"] (B, 256)"""
+    return classifier(_to_shape(cloud, classifier))[1]["retrieval_vectors"].contiguous()
+
+
+class RetrievalEvaluator:
+    """Shape retrieval on the classifier's descriptor (end_points["retrieval_vectors"], pointnet_cls.py:111), all shapes added
+    against each other.  classifier, sampler, match_output: as ClassificationEvaluator; levels: the recall grid l / levels of the
+    precision-recall curve; keep: result() also returns the descriptors and the ranking.  Clouds are (B,N,3); at most 8192 in all."""
+
+    def __init__(self, classifier, sampler=None, match_output=True, levels=20, keep=False):
+        self.classifier, self.sampler = classifier, sampler
+        self.match_output, self.levels, self.keep = bool(match_output), int(levels), bool(keep)
+        self.reset()
+
+    def reset(self):
+        self._desc, self._labels = [], []
+
+    def add(self, x, labels):
+        """One batch: x (B,N,3) and labels (B,) integer class indices on the GPU.  No synchronisation."""
+        if not (x.is_cuda and labels.is_cuda):
+            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        with _EvalMode(self.classifier, self.sampler), torch.no_grad():
+            x = x.contiguous().float()
+            simp, match, _idx, _nun = _sample_with_indices(self.sampler, x)
+            self._desc.append(_descriptors(self.classifier, match if self.match_output else simp))
+            self._labels.append(labels.reshape(-1).int())
+
+    def result(self):
+        """One launch and one device-to-host transfer -> dict: the per-query arrays ap (float64; NaN for a query without a relevant
+        shape), prec (items, levels), n_relevant, labels (int64), retrieval_aggregates of them (map, pr_curve, auc, n_valid); with
+        keep=True also descriptors (items, C) float32 and order (items, items - 1) int64, the ranking of every query."""
+        if not self._desc:
+            raise RuntimeError("RetrievalEvaluator.result: nothing was added")
+        desc, labels = torch.cat(self._desc), torch.cat(self._labels)
+        n, C, L = desc.shape[0], desc.shape[1], self.levels
+        got = ops.retrieval_metrics(desc, labels, L, return_order=self.keep)
+        # (counts, class indices and shape indices are far below 2^24: exact as float32)
+        parts = [got[0], got[1].reshape(-1), got[2].float(), labels.float()]
+        if self.keep:
+            parts += [desc.reshape(-1), got[3].float().reshape(-1)]
+        flat = torch.cat(parts).cpu().numpy()
+        o = n * (L + 1)
+        out = {"ap": flat[:n].astype(np.float64), "prec": flat[n:o].reshape(n, L).astype(np.float64),
+               "n_relevant": flat[o:o + n].astype(np.int64), "labels": flat[o + n:o + 2 * n].astype(np.int64)}
+        if self.keep:
+            o += 2 * n
+            out["descriptors"] = flat[o:o + n * C].reshape(n, C).copy()
+            out["order"] = flat[o + n * C:].astype(np.int64).reshape(n, max(n - 1, 0))
+        out.update(retrieval_aggregates(out["ap"], out["prec"], out["n_relevant"]))
+        return out
+
+
+class ProgressiveRetrievalEvaluator:
+    """The retrieval figures at EVERY sample size from one ranking per batch: the cloud is ranked once (_ranked_cloud), the classifier
+    run on every prefix, the descriptors kept as (sizes, items, C) and scored in ONE launch.  classifier, levels: as
+    RetrievalEvaluator; sampler, sizes: as ProgressiveClassificationEvaluator.  Clouds are (B,N,3)."""
+
+    def __init__(self, classifier, sampler, sizes=None, levels=20):
+        self.classifier, self.sampler = classifier, sampler
+        self.sizes = _default_sizes(sampler, sizes)
+        self.levels = int(levels)
+        self.reset()
+
+    def reset(self):
+        self._desc = {s: [] for s in self.sizes}
+        self._labels = []
+
+    def add(self, x, labels):
+        """One batch: x (B,N,3) and labels (B,) on the GPU: ranked once, described once per size.  No synchronisation."""
+        if not (x.is_cuda and labels.is_cuda):
+            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        with _EvalMode(self.classifier, self.sampler), torch.no_grad():
+            x = x.contiguous().float()
+            ordered, _order, _nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
+            for s in self.sizes:
+                self._desc[s].append(_descriptors(self.classifier, ordered[:, :s].contiguous()))
+            self._labels.append(labels.reshape(-1).int())
+
+    def result(self):
+        """One launch for all sizes and one device-to-host transfer -> {"sizes", "labels", "n_relevant" (the labels alone decide
+        it: the same at every size), "by_size": {s: ap, prec, retrieval_aggregates of them}}."""
+        if not self._labels:
+            raise RuntimeError("ProgressiveRetrievalEvaluator.result: nothing was added")
+        desc = torch.stack([torch.cat(self._desc[s]) for s in self.sizes])
+        labels = torch.cat(self._labels)
+        S, n, L = desc.shape[0], desc.shape[1], self.levels
+        ap, prec, n_relevant = ops.retrieval_metrics(desc, labels, L)
+        flat = torch.cat([ap.reshape(-1), prec.reshape(-1), n_relevant.float(), labels.float()]).cpu().numpy()
+        aps = flat[:S * n].reshape(S, n).astype(np.float64)
+        precs = flat[S * n:S * n * (L + 1)].reshape(S, n, L).astype(np.float64)
+        o = S * n * (L + 1)
+        out = {"sizes": list(self.sizes), "n_relevant": flat[o:o + n].astype(np.int64), "labels": flat[o + n:].astype(np.int64),
+               "by_size": {}}
+        for k, s in enumerate(self.sizes):
+            r = {"ap": aps[k], "prec": precs[k]}
+            r.update(retrieval_aggregates(aps[k], precs[k], out["n_relevant"]))
+            out["by_size"][s] = r
         return out

@@ -381,6 +381,40 @@ def rank_points(xyz, idx, k=None, layout=BNC):
     return out, order, n_unique
 
 
+def retrieval_metrics(desc, labels, levels=20, return_order=False):
+    """All-against-all retrieval inside one labelled set (sn_retrieval_metrics): desc (n,C) or (S,n,C) float32 descriptors -- S sets
+    over the same n shapes --, labels (n,) integers -> (ap (S,n) float32, prec (S,n,levels) float32, n_relevant (n,) int32) and, with
+    return_order, (order (S,n,n-1) int32, sorted_dist (S,n,n-1) float32); without the leading S for a 2-D desc.  Every shape queries the
+    other n - 1, ranked by squared L2 distance (ties to the lower index); ap: the average precision, prec[l-1]: the precision at
+    recall l / levels, both NaN for a query whose label no other shape carries.  n <= 8192, levels <= 64.  One launch, no
+    synchronisation, no gradient."""
+    _need_gpu(desc, labels)
+    desc = _f32c(desc.detach())
+    flat = desc.dim() == 2
+    if flat:
+        desc = desc.unsqueeze(0)
+    if desc.dim() != 3:
+        raise ValueError("retrieval_metrics: desc must be (n,C) or (S,n,C), got %s" % (tuple(desc.shape),))
+    S, n, C = desc.shape
+    labels = labels.detach().reshape(-1).contiguous().int()
+    if labels.numel() != n:
+        raise ValueError("retrieval_metrics: labels must hold one entry per shape")
+    levels, m = int(levels), max(n - 1, 0)
+    dev = desc.device
+    ap = torch.empty(S, n, device=dev, dtype=torch.float32)
+    prec = torch.empty(S, n, levels, device=dev, dtype=torch.float32)
+    n_relevant = torch.empty(n, device=dev, dtype=torch.int32)
+    order = torch.empty(S, n, m, device=dev, dtype=torch.int32) if return_order else None
+    sorted_dist = torch.empty(S, n, m, device=dev, dtype=torch.float32) if return_order else None
+    wsb = lib.sn_workspace_bytes(b"retrieval_metrics", S, n, C, levels)
+    ws = torch.empty(wsb, device=dev, dtype=torch.uint8) if wsb > 0 else None
+    with torch.cuda.device(dev):
+        check(lib.sn_retrieval_metrics(S, n, C, ptr(desc), ptr(labels), levels, ptr(ap), ptr(prec), ptr(n_relevant), ptr(order),
+                                       ptr(sorted_dist), ptr(ws), _stream(desc)), "sn_retrieval_metrics")
+    out = (ap, prec, n_relevant) + ((order, sorted_dist) if return_order else ())
+    return tuple(t[0] if flat and t is not n_relevant else t for t in out)
+
+
 def furthest_point_sample(xyz, npoint, layout=BNC):
     """Farthest-point sampling (no gradient): xyz (B,N,3) [BNC] or (B,3,N) [BCN] -> idx (B,npoint) int32.
 
