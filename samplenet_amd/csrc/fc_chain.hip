@@ -920,6 +920,57 @@ extern "C" int sn_fc_chain_forward_supported(int R, int C0, int H, int nl)
            fc_chain_fwd_lds(C0, H, nl) <= (size_t)160 * 1024 - 64;
 }
 
+// ---- what the three forward entries share (`who` names the entry that was called: its refusals carry that name) ----
+// the per-layer operands as the entries receive them: host arrays of nl device pointers / values
+struct FcLayerTable {
+    const float *const *W, *const *bias, *const *gamma, *const *beta;
+    float *const *running_mean, *const *running_var;
+    long long *const *num_batches_tracked;
+    const float *eps, *momentum;
+    float *const *z, *const *coef;
+};
+
+// validates the table (its arrays themselves are checked by the entry) and packs it into g.L
+static int fc_chain_pack_layers(const char *who, const FcLayerTable &t, FcChainArgs &g)
+{
+    for (int l = 0; l < g.nl; ++l) {
+        SN_REQUIRE_AS(who, t.W[l] && t.bias[l] && t.gamma[l] && t.beta[l] && t.z[l] && t.coef[l], "null layer pointer");
+        SN_REQUIRE_AS(who, !(t.running_mean && t.running_mean[l]) || (t.running_var && t.running_var[l]), "running_mean without running_var");
+        g.L[l] = FcChainLayer{t.W[l], t.bias[l], t.gamma[l], t.beta[l], t.running_mean ? t.running_mean[l] : nullptr,
+                              t.running_var ? t.running_var[l] : nullptr, t.num_batches_tracked ? t.num_batches_tracked[l] : nullptr,
+                              t.z[l], t.coef[l], t.eps[l], t.momentum[l]};
+    }
+    return 0;
+}
+
+// the chain on the max-pool of the conv stack (the two pool entries): B clouds, 128 channels, bn5 the last conv layer's
+// BatchNorm (over its B * N rows)
+static FcChainArgs fc_chain_pool_args(int B, int nconv, long long *acc, const float *pool_val, const BnFwd &bn5, float *pooled,
+                                      int *argsel, float *zsel, int H, int nl, float *xbuf, unsigned *sync)
+{
+    FcChainArgs g{};
+    g.a0 = pooled, g.R = B, g.C0 = 128, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
+    g.P.acc = acc + (size_t)(nconv - 1) * kFxLayer, g.P.zero_ptr = acc + (size_t)(nconv - 2) * kFxLayer, g.P.zero_n = kFxLayer;
+    g.P.keys = reinterpret_cast<const unsigned long long *>(pool_val);  // (B, 2, 128) keys: see sn_conv_stack_forward_bn, pooled == NULL
+    g.P.bn = bn5;
+    g.P.pooled = pooled, g.P.argsel = argsel, g.P.zsel = zsel;
+    return g;
+}
+
+template <int C0T, int NLT, bool POOL = false, bool OUT = false>
+static int fc_chain_launch(const char *who, FcChainArgs &g, sn_stream_t stream)
+{
+    const size_t lds = fc_chain_fwd_lds(g.C0, g.H, g.nl);
+    // (the LDS size depends on the shape: renewed per device whenever a call needs more than was granted)
+    static SnLdsAttrGrow attr;
+    if (sn_lds_attr_grow(attr, (const void *)fc_chain_fwd_kernel<C0T, NLT, POOL, OUT>, lds, who)) return SN_ERR_UNSUPPORTED;
+    g.rinv_rows = 1.0 / (double)g.R, g.unbias = g.R > 1 ? (double)g.R / (double)(g.R - 1) : 1.0;
+    // 8 x (H / 32) blocks: block b lands on XCD b % 8, the b % 8 == 0 ones do the work -- all on one XCD (same L2)
+    hipLaunchKernelGGL((fc_chain_fwd_kernel<C0T, NLT, POOL, OUT>), dim3(8 * (g.H / 32)), dim3(256), lds, (hipStream_t)stream, g);
+    SN_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
 extern "C" int sn_fc_chain_forward(int R, int C0, int H, int nl, const float *a0, const float *const *W, const float *const *bias,
                                    const float *const *gamma, const float *const *beta, float *const *running_mean,
                                    float *const *running_var, long long *const *num_batches_tracked, const float *eps,
@@ -932,32 +983,11 @@ extern "C" int sn_fc_chain_forward(int R, int C0, int H, int nl, const float *a0
     SN_REQUIRE(a0 && W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
     FcChainArgs g{};
     g.a0 = a0, g.R = R, g.C0 = C0, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
-    for (int l = 0; l < nl; ++l) {
-        SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
-        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
-        g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
-                              running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
-                              z[l], coef[l], eps[l], momentum[l]};
-    }
-    const size_t lds = fc_chain_fwd_lds(C0, H, nl);
-    {   // (the LDS size depends on the shape: renewed per device whenever a call needs more than was granted)
-        static SnLdsAttrGrow a0, a1, a2;
-        if (sn_lds_attr_grow(a0, (const void *)fc_chain_fwd_kernel<128, 3>, lds, "sn_fc_chain_forward") ||
-            sn_lds_attr_grow(a1, (const void *)fc_chain_fwd_kernel<256, 3>, lds, "sn_fc_chain_forward") ||
-            sn_lds_attr_grow(a2, (const void *)fc_chain_fwd_kernel<0, 0>, lds, "sn_fc_chain_forward"))
-            return SN_ERR_UNSUPPORTED;
-    }
-    // 8 x (H / 32) blocks: block b lands on XCD b % 8, the b % 8 == 0 ones do the work -- all on one XCD (same L2)
-    g.rinv_rows = 1.0 / (double)R, g.unbias = R > 1 ? (double)R / (double)(R - 1) : 1.0;
-    const dim3 grid(8 * (H / 32)), block(256);
-    if (C0 == 128 && nl == 3)
-        hipLaunchKernelGGL((fc_chain_fwd_kernel<128, 3>), grid, block, lds, (hipStream_t)stream, g);
-    else if (C0 == 256 && nl == 3)
-        hipLaunchKernelGGL((fc_chain_fwd_kernel<256, 3>), grid, block, lds, (hipStream_t)stream, g);
-    else
-        hipLaunchKernelGGL((fc_chain_fwd_kernel<0, 0>), grid, block, lds, (hipStream_t)stream, g);
-    SN_LAUNCH_CHECK();
-    return 0;
+    if (int rc = fc_chain_pack_layers(__func__, {W, bias, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, z, coef}, g))
+        return rc;
+    if (C0 == 128 && nl == 3) return fc_chain_launch<128, 3>(__func__, g, stream);
+    if (C0 == 256 && nl == 3) return fc_chain_launch<256, 3>(__func__, g, stream);
+    return fc_chain_launch<0, 0>(__func__, g, stream);
 }
 
 // sn_fc_chain_forward with the tail of the conv stack in front: sn_conv_stack_forward_bn called with pooled = argsel = zsel =
@@ -986,27 +1016,11 @@ extern "C" int sn_fc_chain_forward_pool(int B, int N, int nconv, long long *acc,
     SN_REQUIRE(acc && pool_val && pool_idx && gamma5 && beta5 && running_mean5 && running_var5 && coef5 && pooled && argsel && zsel,
                "null pointer");
     SN_REQUIRE(W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
-    FcChainArgs g{};
-    g.a0 = pooled, g.R = B, g.C0 = C0, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
-    g.P.acc = acc + (size_t)(nconv - 1) * kFxLayer, g.P.zero_ptr = acc + (size_t)(nconv - 2) * kFxLayer, g.P.zero_n = kFxLayer;
-    g.P.keys = reinterpret_cast<const unsigned long long *>(pool_val);  // (B, 2, 128) keys: see sn_conv_stack_forward_bn, pooled == NULL
-    (void)pool_idx;
-    g.P.bn = BnFwd{gamma5, beta5, running_mean5, running_var5, num_batches_tracked5, coef5, eps5, momentum5, (long long)B * N};
-    g.P.pooled = pooled, g.P.argsel = argsel, g.P.zsel = zsel;
-    for (int l = 0; l < nl; ++l) {
-        SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
-        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
-        g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
-                              running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
-                              z[l], coef[l], eps[l], momentum[l]};
-    }
-    const size_t lds = fc_chain_fwd_lds(C0, H, nl);
-    static SnLdsAttrGrow attr;
-    if (sn_lds_attr_grow(attr, (const void *)fc_chain_fwd_kernel<128, 3, true>, lds, "sn_fc_chain_forward_pool")) return SN_ERR_UNSUPPORTED;
-    g.rinv_rows = 1.0 / (double)B, g.unbias = B > 1 ? (double)B / (double)(B - 1) : 1.0;
-    hipLaunchKernelGGL((fc_chain_fwd_kernel<128, 3, true>), dim3(8 * (H / 32)), dim3(256), lds, (hipStream_t)stream, g);
-    SN_LAUNCH_CHECK();
-    return 0;
+    const BnFwd bn5{gamma5, beta5, running_mean5, running_var5, num_batches_tracked5, coef5, eps5, momentum5, (long long)B * N};
+    FcChainArgs g = fc_chain_pool_args(B, nconv, acc, pool_val, bn5, pooled, argsel, zsel, H, nl, xbuf, sync);
+    if (int rc = fc_chain_pack_layers(__func__, {W, bias, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, z, coef}, g))
+        return rc;
+    return fc_chain_launch<128, 3, true>(__func__, g, stream);
 }
 
 // sn_fc_chain_forward_pool with the head's OUTPUT layer -- Linear (Co x H) + BatchNorm without activation (classification/models/
@@ -1037,28 +1051,12 @@ extern "C" int sn_fc_chain_forward_pool_out(int B, int N, int nconv, long long *
     SN_REQUIRE(W && bias && gamma && beta && eps && momentum && z && coef && xbuf && sync, "null pointer");
     SN_REQUIRE(Wo && bo && gamma_o && beta_o && zo && coef_o && y, "null output-layer pointer");
     SN_REQUIRE(!running_mean_o || running_var_o, "running_mean without running_var (output layer)");
-    FcChainArgs g{};
-    g.a0 = pooled, g.R = B, g.C0 = C0, g.H = H, g.nl = nl, g.xbuf = xbuf, g.sync = sync;
-    g.P.acc = acc + (size_t)(nconv - 1) * kFxLayer, g.P.zero_ptr = acc + (size_t)(nconv - 2) * kFxLayer, g.P.zero_n = kFxLayer;
-    g.P.keys = reinterpret_cast<const unsigned long long *>(pool_val);
-    (void)pool_idx;
-    g.P.bn = BnFwd{gamma5, beta5, running_mean5, running_var5, num_batches_tracked5, coef5, eps5, momentum5, (long long)B * N};
-    g.P.pooled = pooled, g.P.argsel = argsel, g.P.zsel = zsel;
-    for (int l = 0; l < nl; ++l) {
-        SN_REQUIRE(W[l] && bias[l] && gamma[l] && beta[l] && z[l] && coef[l], "null layer pointer");
-        SN_REQUIRE(!(running_mean && running_mean[l]) || (running_var && running_var[l]), "running_mean without running_var");
-        g.L[l] = FcChainLayer{W[l], bias[l], gamma[l], beta[l], running_mean ? running_mean[l] : nullptr,
-                              running_var ? running_var[l] : nullptr, num_batches_tracked ? num_batches_tracked[l] : nullptr,
-                              z[l], coef[l], eps[l], momentum[l]};
-    }
+    const BnFwd bn5{gamma5, beta5, running_mean5, running_var5, num_batches_tracked5, coef5, eps5, momentum5, (long long)B * N};
+    FcChainArgs g = fc_chain_pool_args(B, nconv, acc, pool_val, bn5, pooled, argsel, zsel, H, nl, xbuf, sync);
+    if (int rc = fc_chain_pack_layers(__func__, {W, bias, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, z, coef}, g))
+        return rc;
     g.O = FcChainOut{Wo, bo, gamma_o, beta_o, running_mean_o, running_var_o, num_batches_tracked_o, zo, coef_o, y, eps_o, momentum_o, Co};
-    const size_t lds = fc_chain_fwd_lds(C0, H, nl);
-    static SnLdsAttrGrow attr;
-    if (sn_lds_attr_grow(attr, (const void *)fc_chain_fwd_kernel<128, 3, true, true>, lds, "sn_fc_chain_forward_pool_out")) return SN_ERR_UNSUPPORTED;
-    g.rinv_rows = 1.0 / (double)B, g.unbias = B > 1 ? (double)B / (double)(B - 1) : 1.0;
-    hipLaunchKernelGGL((fc_chain_fwd_kernel<128, 3, true, true>), dim3(8 * (H / 32)), dim3(256), lds, (hipStream_t)stream, g);
-    SN_LAUNCH_CHECK();
-    return 0;
+    return fc_chain_launch<128, 3, true, true>(__func__, g, stream);
 }
 
 // the output BatchNorm's operands of sn_fc_chain_backward_obn (z == NULL: none)

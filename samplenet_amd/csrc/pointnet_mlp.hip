@@ -1541,20 +1541,16 @@ static void launch_fwd(const FwdArgs &g, hipStream_t st, bool few_rows = false)
     }
 }
 
+// the per-layer entries serve both kinds of input: raw (coef_prev == NULL) and relu(bn(Zprev))
+constexpr PModes<ACT_NONE, ACT_BN_RELU> kActModes{};
+
 extern "C" int sn_linear_forward(int R, int Ci, int Co, const float *ain, const float *coef_prev, const float *W,
                                  const float *bias, float *z, float *stats, sn_stream_t stream)
 {
     SN_REQUIRE(R >= 1 && Ci >= 1 && Co >= 1, "bad size");
     SN_REQUIRE(ain && W && z, "null pointer");
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = stats;
-    hipStream_t st = (hipStream_t)stream;
-    if (coef_prev)
-        launch_fwd<ACT_BN_RELU>(g, st);
-    else
-        launch_fwd<ACT_NONE>(g, st);
+    const FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, stats);
+    dispatch_act(kActModes, coef_prev != nullptr, [&](auto am) { launch_fwd<decltype(am)::value>(g, (hipStream_t)stream); });
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -1564,14 +1560,8 @@ extern "C" int sn_linear_forward_rows(int R, int Ci, int Co, const float *ain, c
 {
     SN_REQUIRE(R >= 1 && Ci >= 1 && Co >= 1, "bad size");
     SN_REQUIRE(ain && W && z, "null pointer");
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = nullptr;
-    if (coef_prev)
-        launch_fwd<ACT_BN_RELU>(g, (hipStream_t)stream, true);
-    else
-        launch_fwd<ACT_NONE>(g, (hipStream_t)stream, true);
+    const FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, nullptr);
+    dispatch_act(kActModes, coef_prev != nullptr, [&](auto am) { launch_fwd<decltype(am)::value>(g, (hipStream_t)stream, true); });
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -1614,10 +1604,7 @@ extern "C" int sn_linear_forward_maxpool(int R, int Ci, int Co, int npts, const 
         const hipError_t e = hipMemsetAsync(keys, 0, (size_t)B * 2 * Co * sizeof(unsigned long long), st);
         if (e != hipSuccess) return sn_set_error((int)e, "%s: %s", __func__, hipGetErrorString(e));
     }
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = nullptr;  // z == NULL: the activations are not written at all
+    FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, nullptr);  // z == NULL: the activations are not written at all
     g.pool_keys = keys, g.pool_npts = npts, g.pool_max_only = 1;
     launch_fwd<ACT_BN_RELU>(g, st);
     hipLaunchKernelGGL(maxpool_keys_decode_kernel, dim3((B * Co + 255) / 256), dim3(256), 0, st, B * Co, Co, keys, pooled, argsel, zsel);
@@ -1637,25 +1624,21 @@ extern "C" int sn_layer_forward_bn(int R, int Ci, int Co, const float *ain, cons
 {
     SN_REQUIRE(R >= 1 && Ci >= 1 && Co >= 1, "bad size");
     SN_REQUIRE(ain && W && z && stats && gamma && beta && coef, "null pointer");
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = stats;
+    FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, stats);
     const BnFwd bn{gamma, beta, running_mean, running_var, num_batches_tracked, coef, eps, momentum, (long long)R};
     hipStream_t st = (hipStream_t)stream;
     if (R > 32 && R <= 64 && (Ci == 64 || Ci == 128 || Ci == 256)) {  // both halves in one workgroup, BatchNorm finalised in the epilogue
         g.bn = bn;
         g.stats = nullptr;
         const size_t lds = ((size_t)96 * (Ci + 4) + 2 * 3 * 16 * 64 + 64 * 36) * sizeof(float);
-        static SnLdsAttr attr[2];
         const size_t mx = ((size_t)96 * 260 + 2 * 3 * 16 * 64 + 64 * 36) * sizeof(float);
-        if (sn_lds_attr(attr[coef_prev ? 1 : 0], coef_prev ? (const void *)rows64_fwd_kernel<ACT_BN_RELU> : (const void *)rows64_fwd_kernel<ACT_NONE>,
-                        mx, "rows64_fwd_kernel"))
-            return SN_ERR_UNSUPPORTED;
-        if (coef_prev)
-            hipLaunchKernelGGL((rows64_fwd_kernel<ACT_BN_RELU>), dim3((Co + 31) / 32), dim3(256), lds, st, g);
-        else
-            hipLaunchKernelGGL((rows64_fwd_kernel<ACT_NONE>), dim3((Co + 31) / 32), dim3(256), lds, st, g);
+        bool refused = false;
+        dispatch_act(kActModes, coef_prev != nullptr, [&](auto am) {
+            static SnLdsAttr attr;  // (one per instantiation of this body: per kernel)
+            refused = sn_lds_attr(attr, (const void *)rows64_fwd_kernel<decltype(am)::value>, mx, "rows64_fwd_kernel") != 0;
+            if (!refused) hipLaunchKernelGGL((rows64_fwd_kernel<decltype(am)::value>), dim3((Co + 31) / 32), dim3(256), lds, st, g);
+        });
+        if (refused) return SN_ERR_UNSUPPORTED;
         SN_LAUNCH_CHECK();
         return 0;
     }
@@ -1663,10 +1646,7 @@ extern "C" int sn_layer_forward_bn(int R, int Ci, int Co, const float *ain, cons
         g.bn = bn;
         g.stats = nullptr;
     }
-    if (coef_prev)
-        launch_fwd<ACT_BN_RELU>(g, st);
-    else
-        launch_fwd<ACT_NONE>(g, st);
+    dispatch_act(kActModes, coef_prev != nullptr, [&](auto am) { launch_fwd<decltype(am)::value>(g, st); });
     if (R > 32)
         hipLaunchKernelGGL(bn_finalize_kernel, dim3((Co + kChan - 1) / kChan), dim3(1024), 0, st, sn_linear_stats_blocks(R), Co, stats, bn);
     SN_LAUNCH_CHECK();
@@ -1688,10 +1668,7 @@ extern "C" int sn_conv_forward_bn_pool(int R, int Ci, int Co, int npts, const fl
                "null pointer");
     if (R <= 64 || R % 64 || npts % 64 || R % npts || Co % 64 || Ci % 64)
         return sn_set_error(SN_ERR_UNSUPPORTED, "sn_conv_forward_bn_pool: needs 64-aligned rows / points / channels");
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = stats;
+    FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, stats);
     g.pool_val = pool_val, g.pool_idx = pool_idx, g.pool_npts = npts;
     const BnFwd bn{gamma, beta, running_mean, running_var, num_batches_tracked, coef, eps, momentum, (long long)R};
     hipStream_t st = (hipStream_t)stream;
@@ -1792,6 +1769,16 @@ static int launch_fwd_persist(const FwdArgs &g, int ntiles, int tpw, int nwg, hi
     return 0;
 }
 
+// a statistics-chain layer of the stack on whole tiles; with the pre-split weight planes (g.wplanes) the PLANES form of the kernel
+template <class TT, int KT>
+static void launch_fwd_fx(const FwdArgs &g, dim3 grid, size_t lds, hipStream_t st)
+{
+    if (g.wplanes)
+        hipLaunchKernelGGL((linear_fwd_kernel<TT, true, ACT_BN_RELU_FX, KT, SN_BF16X3 != 0>), grid, dim3(TT::THREADS), lds, st, g);
+    else
+        hipLaunchKernelGGL((linear_fwd_kernel<TT, true, ACT_BN_RELU_FX, KT>), grid, dim3(TT::THREADS), lds, st, g);
+}
+
 extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *channels, const float *x, const float *const *W,
                                         const float *const *bias, const float *const *gamma, const float *const *beta,
                                         float *const *running_mean, float *const *running_var,
@@ -1859,10 +1846,7 @@ extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *ch
     using T = TileBig;
     for (int l = 1; l < nlayers; ++l) {
         const int Ci = channels[l], Co = channels[l + 1];
-        FwdArgs g{};
-        g.a = make_act(z[l - 1], nullptr, R, Ci);
-        g.w.w = W[l], g.w.co = Co, g.w.ci = Ci;
-        g.bias = bias ? bias[l] : nullptr, g.z = z[l], g.stats = nullptr;
+        FwdArgs g = make_fwd(R, Ci, Co, z[l - 1], nullptr, W[l], bias ? bias[l] : nullptr, z[l], nullptr);
         g.acc_in = acc + (size_t)(l - 1) * S, g.bn_prev = bn_of(l - 1), g.acc_out = acc + (size_t)l * S;
         if (l >= 2) g.zero_ptr = acc + (size_t)(l - 2) * S, g.zero_n = (int)S;
         if (l == nlayers - 1) {
@@ -1912,25 +1896,19 @@ extern "C" int sn_conv_stack_forward_bn(int B, int N, int nlayers, const int *ch
             using TW = TileWide;
             const dim3 grid(R / TW::BM, Co / TW::BN);
             const size_t lds = shaped_lds(lds_bytes<TW>() + (size_t)2 * Ci * sizeof(float), grid);
-#define SN_FWD_FX(TT, KT_)                                                                                                \
-    do {                                                                                                                  \
-        if (pl) hipLaunchKernelGGL((linear_fwd_kernel<TT, true, ACT_BN_RELU_FX, KT_, SN_BF16X3 != 0>), grid, dim3(TT::THREADS), lds, st, g); \
-        else hipLaunchKernelGGL((linear_fwd_kernel<TT, true, ACT_BN_RELU_FX, KT_>), grid, dim3(TT::THREADS), lds, st, g);  \
-    } while (0)
             if (Ci == 256) {  // (sn_conv_stack_forward_supported: wide layers only with the planes)
                 SN_REQUIRE(pl, "a 256-channel input needs the pre-split weight planes");
                 hipLaunchKernelGGL((linear_fwd_kernel<TW, true, ACT_BN_RELU_FX, 256, SN_BF16X3 != 0>), grid, dim3(TW::THREADS), lds, st, g);
-            } else if (Ci == 128 && pl) SN_FWD_FX(TW, 128);
-            else if (Ci == 128) SN_FWD_FX(TW, 0);  // chunk-by-chunk prefetch (fetching the whole K = 128 up front measured slower)
-            else SN_FWD_FX(TW, 64);
+            } else if (Ci == 128 && pl) launch_fwd_fx<TW, 128>(g, grid, lds, st);
+            else if (Ci == 128) launch_fwd_fx<TW, 0>(g, grid, lds, st);  // chunk-by-chunk prefetch (fetching the whole K = 128 up front measured slower)
+            else launch_fwd_fx<TW, 64>(g, grid, lds, st);
             continue;
         }
         const dim3 grid(R / T::BM, Co / T::BN);
         const size_t lds = shaped_lds(lds_bytes<T>() + (size_t)2 * Ci * sizeof(float), grid);
-        if (Ci == 128 && pl) SN_FWD_FX(T, 128);
-        else if (Ci == 128) SN_FWD_FX(T, 0);  // (chunk-by-chunk, as above)
-        else SN_FWD_FX(T, 64);
-#undef SN_FWD_FX
+        if (Ci == 128 && pl) launch_fwd_fx<T, 128>(g, grid, lds, st);
+        else if (Ci == 128) launch_fwd_fx<T, 0>(g, grid, lds, st);  // (chunk-by-chunk, as above)
+        else launch_fwd_fx<T, 64>(g, grid, lds, st);
     }
     const int Cn = channels[nlayers];
     long long *zp = nlayers >= 2 ? acc + (size_t)(nlayers - 2) * S : nullptr;
@@ -1993,17 +1971,11 @@ extern "C" int sn_layer_forward_bn_out(int R, int Ci, int Co, const float *ain, 
     SN_REQUIRE(ain && W && z && gamma && beta && coef && y, "null pointer");
     if (R > 32 || Ci < 64 || Ci > 512 || (Ci & (Ci - 1)))
         return sn_set_error(SN_ERR_UNSUPPORTED, "sn_layer_forward_bn_out: R <= 32 rows, Ci a power of two in 64 .. 512");
-    FwdArgs g{};
-    g.a = make_act(ain, coef_prev, R, Ci);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.bias = bias, g.z = z, g.stats = nullptr;
+    FwdArgs g = make_fwd(R, Ci, Co, ain, coef_prev, W, bias, z, nullptr);
     g.bn = BnFwd{gamma, beta, running_mean, running_var, num_batches_tracked, coef, eps, momentum, (long long)R};
     g.bn_y = y;
     hipStream_t st = (hipStream_t)stream;
-    if (coef_prev)
-        launch_fwd<ACT_BN_RELU>(g, st);
-    else
-        launch_fwd<ACT_NONE>(g, st);
+    dispatch_act(kActModes, coef_prev != nullptr, [&](auto am) { launch_fwd<decltype(am)::value>(g, st); });
     SN_LAUNCH_CHECK();
     return 0;
 }

@@ -2040,15 +2040,35 @@ __global__ void __launch_bounds__(1024) pool_bwd_kernel(int B, int C, const floa
 
 }  // namespace sn
 
-static DzSrc make_dz(int mode, const float *dy, const float *z, const float *kcoef, const float *gsel, const int *argsel,
-                     int rows, int ch, int npts)
+// ---- this unit's argument blocks (DgradArgs / WgradArgs are declared above, so their builders stand here and not in mlp_host.h) ----
+static DgradArgs make_dgrad(const DzSrc &dz, int Ci, const float *W, const float *zprev, const float *coef_prev, float *dyprev,
+                            float *stats)
 {
-    DzSrc d{};
-    d.mode = mode, d.dy = dy, d.z = z, d.rows = rows, d.ch = ch, d.npts = npts > 0 ? npts : 1;
-    d.k1 = kcoef, d.k2 = kcoef ? kcoef + ch : nullptr, d.k3 = kcoef ? kcoef + 2 * ch : nullptr;
-    d.gsel = gsel, d.argsel = argsel;
-    return d;
+    DgradArgs g{};
+    g.dz = dz;
+    g.w.w = W, g.w.co = dz.ch, g.w.ci = Ci;
+    g.prev = make_act(zprev, coef_prev, dz.rows, Ci);
+    g.dyprev = dyprev, g.stats = stats;
+    return g;
 }
+
+// dz: the dgrad side's.  bias: a column of ones behind the Ci inputs (its products are the bias gradient).  part / rows_per_split:
+// the split-K routes only
+static WgradArgs make_wgrad(const DzSrc &dz, int Ci, const float *aprev, const float *coef_prev, bool bias, float *part = nullptr,
+                            int rows_per_split = 0)
+{
+    WgradArgs g{};
+    g.dz = dz;
+    g.prev = make_act(aprev, coef_prev, dz.rows, Ci, bias ? Ci : -1);
+    g.ncols = Ci + (bias ? 1 : 0);
+    g.part = part, g.rows_per_split = rows_per_split;
+    return g;
+}
+
+// Workgroups of the closing weight-gradient reduction over nel = Co * Ci elements: kRedElems elements each on the 16-byte path
+// (wgrad_reduce_block), 64 each on post_bwd_kernel's scalar path (nel % 4 != 0).  post_bwd_in3_kernel has the 16-byte path alone and
+// its callers wrote the first form only: for their shapes (channel counts in multiples of 64) the two forms are the same number.
+static int wgrad_reduce_blocks(int nel) { return nel % 4 == 0 ? (nel + kRedElems - 1) / kRedElems : (nel + 63) / 64; }
 
 template <int ZMODE, int PMODE>
 static void launch_dgrad(const DgradArgs &g, hipStream_t st)
@@ -2077,20 +2097,9 @@ extern "C" int sn_linear_dgrad(int R, int Ci, int Co, int dz_mode, const float *
     SN_REQUIRE(R >= 1 && Ci >= 1 && Co >= 1, "bad size");
     SN_REQUIRE(W && dyprev, "null pointer");
     SN_REQUIRE(dz_mode >= DZ_PLAIN && dz_mode <= DZ_POOL, "bad dz_mode");
-    DgradArgs g{};
-    g.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.prev = make_act(zprev, coef_prev, R, Ci);
-    g.dyprev = dyprev, g.stats = stats;
-    hipStream_t st = (hipStream_t)stream;
-    const bool pm = coef_prev != nullptr;
-    if (dz_mode == DZ_PLAIN) {
-        if (pm) launch_dgrad<DZ_PLAIN, ACT_BN_RELU>(g, st); else launch_dgrad<DZ_PLAIN, ACT_NONE>(g, st);
-    } else if (dz_mode == DZ_BN) {
-        if (pm) launch_dgrad<DZ_BN, ACT_BN_RELU>(g, st); else launch_dgrad<DZ_BN, ACT_NONE>(g, st);
-    } else {
-        if (pm) launch_dgrad<DZ_POOL, ACT_BN_RELU>(g, st); else launch_dgrad<DZ_POOL, ACT_NONE>(g, st);
-    }
+    const DgradArgs g = make_dgrad(make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts), Ci, W, zprev, coef_prev, dyprev, stats);
+    dispatch_modes(ZModes<DZ_PLAIN, DZ_BN, DZ_POOL>{}, PModes<ACT_NONE, ACT_BN_RELU>{}, dz_mode, coef_prev != nullptr,
+                   [&](auto zm, auto pm) { launch_dgrad<decltype(zm)::value, decltype(pm)::value>(g, (hipStream_t)stream); });
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -2110,33 +2119,14 @@ static bool conv_bwd_fused_shape(int R, int Ci, int Co)
 // persistent workgroups: one per CU (each walks over ceil(tiles / groups) 64-row tiles)
 static int conv_bwd_fused_groups(int R) { return std::min((R + 63) / 64, device_cus()); }
 
-template <int CI, int CO, int ZMODE>
-static void launch_conv_bwd_bx3_t(const ConvBwdArgs &a, int G, bool fullr, hipStream_t st)
-{
-    constexpr size_t lds = CbxShape<CI, CO>::LDS_BYTES;
-    // (a refused request leaves the error text; the launch below then fails and the entry point's launch check reports it)
-    static SnLdsAttr at, af;
-    (void)sn_lds_attr(at, (const void *)conv_bwd_bx3_kernel<CI, CO, ZMODE, true>, lds, "conv_bwd_bx3_kernel");
-    (void)sn_lds_attr(af, (const void *)conv_bwd_bx3_kernel<CI, CO, ZMODE, false>, lds, "conv_bwd_bx3_kernel");
-    if (fullr)
-        hipLaunchKernelGGL((conv_bwd_bx3_kernel<CI, CO, ZMODE, true>), dim3(G), dim3(512), lds, st, a);
-    else
-        hipLaunchKernelGGL((conv_bwd_bx3_kernel<CI, CO, ZMODE, false>), dim3(G), dim3(512), lds, st, a);
-}
-
 #if SN_BF16X3
 // one pass of the 128 x 128 kernel over a half of a 256-channel side (see conv_bwd_bx3_kernel)
 template <int ZMODE, int GZ, int GP, int GW, int DM>
 static void launch_conv_bwd_bx3_half(const ConvBwdArgs &a, int G, bool fullr, hipStream_t st)
 {
-    constexpr size_t lds = CbxShape<128, 128>::LDS_BYTES;
-    static SnLdsAttr at, af;
-    (void)sn_lds_attr(at, (const void *)conv_bwd_bx3_kernel<128, 128, ZMODE, true, false, false, GZ, GP, GW, DM>, lds, "conv_bwd_bx3_kernel");
-    (void)sn_lds_attr(af, (const void *)conv_bwd_bx3_kernel<128, 128, ZMODE, false, false, false, GZ, GP, GW, DM>, lds, "conv_bwd_bx3_kernel");
-    if (fullr)
-        hipLaunchKernelGGL((conv_bwd_bx3_kernel<128, 128, ZMODE, true, false, false, GZ, GP, GW, DM>), dim3(G), dim3(512), lds, st, a);
-    else
-        hipLaunchKernelGGL((conv_bwd_bx3_kernel<128, 128, ZMODE, false, false, false, GZ, GP, GW, DM>), dim3(G), dim3(512), lds, st, a);
+    launch_lds_twins<conv_bwd_bx3_kernel<128, 128, ZMODE, true, false, false, GZ, GP, GW, DM>,
+                     conv_bwd_bx3_kernel<128, 128, ZMODE, false, false, false, GZ, GP, GW, DM>>(
+        fullr, dim3(G), dim3(512), CbxShape<128, 128>::LDS_BYTES, "conv_bwd_bx3_kernel", st, a);
 }
 #endif
 
@@ -2144,18 +2134,17 @@ template <int CI, int CO, int ZMODE>
 static void launch_conv_bwd_fused_t(const ConvBwdArgs &a, int G, bool fullr, hipStream_t st)
 {
 #if SN_BF16X3
-    launch_conv_bwd_bx3_t<CI, CO, ZMODE>(a, G, fullr, st);
+    launch_lds_twins<conv_bwd_bx3_kernel<CI, CO, ZMODE, true>, conv_bwd_bx3_kernel<CI, CO, ZMODE, false>>(
+        fullr, dim3(G), dim3(512), CbxShape<CI, CO>::LDS_BYTES, "conv_bwd_bx3_kernel", st, a);
     return;
 #endif
-    constexpr size_t lds = CbfShape<CI, CO>::LDS_BYTES;
-    static SnLdsAttr at, af;  // more than 64 KB of dynamic LDS must be requested explicitly, per device
-    (void)sn_lds_attr(at, (const void *)conv_bwd_fused_kernel<CI, CO, ZMODE, true>, lds, "conv_bwd_fused_kernel");
-    (void)sn_lds_attr(af, (const void *)conv_bwd_fused_kernel<CI, CO, ZMODE, false>, lds, "conv_bwd_fused_kernel");
-    if (fullr)
-        hipLaunchKernelGGL((conv_bwd_fused_kernel<CI, CO, ZMODE, true>), dim3(G), dim3(512), lds, st, a);
-    else
-        hipLaunchKernelGGL((conv_bwd_fused_kernel<CI, CO, ZMODE, false>), dim3(G), dim3(512), lds, st, a);
+    launch_lds_twins<conv_bwd_fused_kernel<CI, CO, ZMODE, true>, conv_bwd_fused_kernel<CI, CO, ZMODE, false>>(
+        fullr, dim3(G), dim3(512), CbfShape<CI, CO>::LDS_BYTES, "conv_bwd_fused_kernel", st, a);
 }
+
+// the dZ forms the fused kernels are built for (conv_bwd_fused_ok admits no other), always above a BatchNorm + ReLU
+constexpr ZModes<DZ_BN, DZ_POOL> kConvBwdDz{};
+constexpr PModes<ACT_BN_RELU> kBnBelow{};
 
 // returns the number of workgroups (= partials in `stats` and `part`)
 static int launch_conv_bwd_fused(int R, int Ci, int Co, int dz_mode, const float *dy, const float *z, const float *kcoef,
@@ -2165,9 +2154,7 @@ static int launch_conv_bwd_fused(int R, int Ci, int Co, int dz_mode, const float
 {
     ConvBwdArgs a{};
     if (fx) a.acc_in = fx->acc_in, a.bb_in = fx->bb_in, a.acc_out = fx->acc_out, a.zero_ptr = fx->zero_ptr, a.zero_n = fx->zero_n;
-    a.dz.mode = dz_mode, a.dz.dy = dy, a.dz.z = z, a.dz.rows = R, a.dz.ch = Co, a.dz.npts = npts > 0 ? npts : 1;
-    a.dz.k1 = kcoef, a.dz.k2 = kcoef ? kcoef + Co : nullptr, a.dz.k3 = kcoef ? kcoef + 2 * Co : nullptr;
-    a.dz.gsel = gsel, a.dz.argsel = argsel;
+    a.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
     a.W = W, a.zprev = zprev, a.scale_prev = coef_prev, a.shift_prev = coef_prev + Ci;
     a.dyprev = dyprev, a.stats = stats, a.part = part;
 #if SN_BF16X3
@@ -2197,22 +2184,19 @@ static int launch_conv_bwd_fused(int R, int Ci, int Co, int dz_mode, const float
                 b.scale_prev = coef_prev + 128 * hh, b.shift_prev = coef_prev + 256 + 128 * hh;
                 b.stats = stats + 128 * hh, b.stats_ld = 256;
                 b.part = part + 128 * hh, b.part_wg_stride = 128 * 256, b.part_ld = 256;
-                if (dz_mode == DZ_BN) launch_conv_bwd_bx3_half<DZ_BN, 128, 256, 256, 0>(b, G, f32, st);
-                else launch_conv_bwd_bx3_half<DZ_POOL, 128, 256, 256, 0>(b, G, f32, st);
+                dispatch_modes(kConvBwdDz, kBnBelow, dz_mode, true,
+                               [&](auto zm, auto) { launch_conv_bwd_bx3_half<decltype(zm)::value, 128, 256, 256, 0>(b, G, f32, st); });
             }
         }
         return G;
     }
 #endif
-#define SN_CBF(CI_, CO_)                                                                       \
-    do {                                                                                       \
-        if (dz_mode == DZ_BN) launch_conv_bwd_fused_t<CI_, CO_, DZ_BN>(a, G, fullr, st);        \
-        else launch_conv_bwd_fused_t<CI_, CO_, DZ_POOL>(a, G, fullr, st);                       \
-    } while (0)
-    if (Ci == 64 && Co == 64) SN_CBF(64, 64);
-    else if (Ci == 64 && Co == 128) SN_CBF(64, 128);
-    else SN_CBF(128, 128);
-#undef SN_CBF
+    dispatch_modes(kConvBwdDz, kBnBelow, dz_mode, true, [&](auto zm, auto) {
+        constexpr int ZM = decltype(zm)::value;
+        if (Ci == 64 && Co == 64) launch_conv_bwd_fused_t<64, 64, ZM>(a, G, fullr, st);
+        else if (Ci == 64 && Co == 128) launch_conv_bwd_fused_t<64, 128, ZM>(a, G, fullr, st);
+        else launch_conv_bwd_fused_t<128, 128, ZM>(a, G, fullr, st);
+    });
     return G;
 }
 
@@ -2244,9 +2228,7 @@ static void launch_wgrad(WgradArgs &g, int R, int Ci, int Co, int with_bias, flo
         return;
     }
     const int nsplit = sn_linear_wgrad_splits(R, Ci, Co, with_bias);
-    int rps = (R + nsplit - 1) / nsplit;
-    rps = ((rps + BK - 1) / BK) * BK;
-    g.rows_per_split = rps;
+    const int rps = g.rows_per_split = wgrad_rows_per_split(R, nsplit);
     if (ZMODE == DZ_BN && PMODE == ACT_NONE && Ci == 3 && !with_bias) {  // xyz input layer
         hipLaunchKernelGGL(conv_in3_wgrad_kernel, dim3(nsplit, (Co + 63) / 64), dim3(256), 0, st, R, Co, rps, g.prev.z, g.dz.dy,
                            g.dz.z, g.dz.k1, g.part);
@@ -2270,23 +2252,10 @@ extern "C" int sn_linear_wgrad(int R, int Ci, int Co, int dz_mode, const float *
     SN_REQUIRE(aprev && part && dW, "null pointer");
     SN_REQUIRE(dz_mode >= DZ_PLAIN && dz_mode <= DZ_POOL, "bad dz_mode");
     const int with_bias = db != nullptr;
-    WgradArgs g{};
-    g.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
-    g.prev = make_act(aprev, coef_prev, R, Ci, with_bias ? Ci : -1);
-    g.ncols = Ci + with_bias;
-    g.part = part;
-    hipStream_t st = (hipStream_t)stream;
-    const bool pm = coef_prev != nullptr;
-    if (dz_mode == DZ_PLAIN) {
-        if (pm) launch_wgrad<DZ_PLAIN, ACT_BN_RELU>(g, R, Ci, Co, with_bias, dW, db, st);
-        else launch_wgrad<DZ_PLAIN, ACT_NONE>(g, R, Ci, Co, with_bias, dW, db, st);
-    } else if (dz_mode == DZ_BN) {
-        if (pm) launch_wgrad<DZ_BN, ACT_BN_RELU>(g, R, Ci, Co, with_bias, dW, db, st);
-        else launch_wgrad<DZ_BN, ACT_NONE>(g, R, Ci, Co, with_bias, dW, db, st);
-    } else {
-        if (pm) launch_wgrad<DZ_POOL, ACT_BN_RELU>(g, R, Ci, Co, with_bias, dW, db, st);
-        else launch_wgrad<DZ_POOL, ACT_NONE>(g, R, Ci, Co, with_bias, dW, db, st);
-    }
+    WgradArgs g = make_wgrad(make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts), Ci, aprev, coef_prev, with_bias, part);
+    dispatch_modes(ZModes<DZ_PLAIN, DZ_BN, DZ_POOL>{}, PModes<ACT_NONE, ACT_BN_RELU>{}, dz_mode, coef_prev != nullptr, [&](auto zm, auto pm) {
+        launch_wgrad<decltype(zm)::value, decltype(pm)::value>(g, R, Ci, Co, with_bias, dW, db, (hipStream_t)stream);
+    });
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -2329,34 +2298,40 @@ static int launch_rows_bwd(int R, int Ci, int Co, int dz_mode, const float *dy, 
                            const float *zprev, const float *coef_prev, float *dyprev, float *stats, float *dW, float *db, hipStream_t st,
                            const BnBwd *finalize = nullptr)
 {
-    DgradArgs g{};
+    DgradArgs g = make_dgrad(make_dz(dz_mode, dy, z, kcoef, nullptr, nullptr, R, Co, 1), Ci, W, zprev, coef_prev, dyprev, stats);
     if (finalize) g.bb = *finalize;  // (R <= 64 only: one row block holds every row)
-    g.dz = make_dz(dz_mode, dy, z, kcoef, nullptr, nullptr, R, Co, 1);
-    g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-    g.prev = make_act(zprev, coef_prev, R, Ci);
-    g.dyprev = dyprev, g.stats = stats;
-    WgradArgs wg{};
-    wg.dz = g.dz;
-    wg.prev = make_act(zprev, coef_prev, R, Ci, db ? Ci : -1);
-    wg.ncols = Ci + (db ? 1 : 0);
+    const WgradArgs wg = make_wgrad(g.dz, Ci, zprev, coef_prev, db != nullptr);
     const int tm = (Co + 31) / 32, tn = (wg.ncols + 31) / 32, ntiles = tm * tn;
     const int ncb = (Ci + 31) / 32, nrb = (R + 63) / 64, n_d = ncb * nrb, n_w = (ntiles + 3) / 4;
     const dim3 grid(n_d + n_w), block(256);
-    const bool pm = coef_prev != nullptr, vec = Co % 64 == 0;
-#define SN_RB(ZM, PM)                                                                                                        \
-    do {                                                                                                                     \
-        if (vec)                                                                                                             \
-            hipLaunchKernelGGL((rows_bwd_kernel<ZM, PM, true>), grid, block, 0, st, g, wg, dW, db, tn, ntiles, n_d, ncb);     \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((rows_bwd_kernel<ZM, PM, false>), grid, block, 0, st, g, wg, dW, db, tn, ntiles, n_d, ncb);    \
-    } while (0)
-    if (dz_mode == DZ_PLAIN) {
-        if (pm) SN_RB(DZ_PLAIN, ACT_BN_RELU); else SN_RB(DZ_PLAIN, ACT_NONE);
-    } else {
-        if (pm) SN_RB(DZ_BN, ACT_BN_RELU); else SN_RB(DZ_BN, ACT_NONE);
-    }
-#undef SN_RB
+    // (never the pool form: rows_bwd_shape)
+    dispatch_modes(ZModes<DZ_PLAIN, DZ_BN>{}, PModes<ACT_NONE, ACT_BN_RELU>{}, dz_mode, coef_prev != nullptr, Co % 64 == 0,
+                   [&](auto zm, auto pm, auto vec) {
+                       hipLaunchKernelGGL((rows_bwd_kernel<decltype(zm)::value, decltype(pm)::value, decltype(vec)::value>), grid, block, 0, st, g,
+                                          wg, dW, db, tn, ntiles, n_d, ncb);
+                   });
     return nrb;
+}
+
+// The combined dgrad + wgrad launch (linear_bwd_kernel) on whole tiles above a BatchNorm + ReLU, for the dZ forms `zl` the calling
+// route admits.  -> the number of statistics partials it fills: one per TileBig row block
+template <class ZL>
+static int launch_linear_bwd(ZL zl, const DzSrc &dz, int Ci, const float *W, const float *zprev, const float *coef_prev, float *dyprev,
+                             float *stats, float *part, int nsplit, int rps, hipStream_t st)
+{
+    const int R = dz.rows, Co = dz.ch;
+    const DgradArgs d = make_dgrad(dz, Ci, W, zprev, coef_prev, dyprev, stats);
+    const WgradArgs w = make_wgrad(dz, Ci, zprev, coef_prev, false, part, rps);
+    const int wgx = Co / TileW::BM, wgy = Ci / TileW::BN, n_w = wgx * wgy * nsplit;
+    const int dgx = R / TileBig::BM, n_d = dgx * (Ci / TileBig::BN);
+    const dim3 grid(n_w + n_d);
+    const size_t lds = shaped_lds(std::max(lds_bytes<TileBig>(), lds_bytes<TileW>()), grid);
+    static_assert(TileBig::THREADS == TileW::THREADS, "combined backward kernel needs one workgroup size");
+    dispatch_modes(zl, PModes<ACT_BN_RELU>{}, dz.mode, true, [&](auto zm, auto pm) {
+        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, decltype(zm)::value, decltype(pm)::value>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w,
+                           wgx, wgy, dgx);
+    });
+    return dgx;
 }
 
 extern "C" int sn_linear_backward(int R, int Ci, int Co, int dz_mode, const float *dy, const float *z, const float *kcoef,
@@ -2383,8 +2358,7 @@ extern "C" int sn_linear_backward(int R, int Ci, int Co, int dz_mode, const floa
         return 0;
     }
     const int nsplit = sn_linear_wgrad_splits(R, Ci, Co, 0);
-    int rps = (R + nsplit - 1) / nsplit;
-    rps = ((rps + BK - 1) / BK) * BK;
+    const int rps = wgrad_rows_per_split(R, nsplit);
     const bool fast = R > 64 && coef_prev && dz_mode != DZ_PLAIN && R % TileBig::BM == 0 && Ci % TileBig::BN == 0 &&
                       Co % BK == 0 && Co % TileW::BM == 0 && Ci % TileW::BN == 0 && R % rps == 0;
     if (!fast) {
@@ -2393,24 +2367,9 @@ extern "C" int sn_linear_backward(int R, int Ci, int Co, int dz_mode, const floa
         return sn_linear_dgrad(R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev, stats, stream);
     }
     hipStream_t st = (hipStream_t)stream;
-    DgradArgs d{};
-    d.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
-    d.w.w = W, d.w.co = Co, d.w.ci = Ci;
-    d.prev = make_act(zprev, coef_prev, R, Ci);
-    d.dyprev = dyprev, d.stats = stats;
-    WgradArgs w{};
-    w.dz = d.dz;
-    w.prev = make_act(zprev, coef_prev, R, Ci, -1);
-    w.ncols = Ci, w.part = part, w.rows_per_split = rps;
-    const int wgx = Co / TileW::BM, wgy = Ci / TileW::BN, n_w = wgx * wgy * nsplit;
-    const int dgx = R / TileBig::BM, n_d = dgx * (Ci / TileBig::BN);
-    const dim3 grid(n_w + n_d);
-    const size_t lds = shaped_lds(std::max(lds_bytes<TileBig>(), lds_bytes<TileW>()), grid);
-    static_assert(TileBig::THREADS == TileW::THREADS, "combined backward kernel needs one workgroup size");
-    if (dz_mode == DZ_BN)
-        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, DZ_BN, ACT_BN_RELU>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w, wgx, wgy, dgx);
-    else
-        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, DZ_POOL, ACT_BN_RELU>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w, wgx, wgy, dgx);
+    // (fast: no plain dZ)
+    launch_linear_bwd(ZModes<DZ_BN, DZ_POOL>{}, make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts), Ci, W, zprev, coef_prev, dyprev, stats,
+                      part, nsplit, rps, st);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((Co * Ci + 63) / 64), dim3(1024), 0, st, nsplit, Co, Ci, Ci, part, dW, nullptr);
     SN_LAUNCH_CHECK();
     return 0;
@@ -2440,35 +2399,17 @@ extern "C" int sn_layer_backward(int R, int Ci, int Co, int dz_mode, const float
     const BnBwd bb{coef_prev, prev_dgamma, prev_dbeta, prev_dbias, prev_kcoef,
                    prev_bn_rows > 0 ? prev_bn_rows : (prev_bn_rows < 0 ? -1ll : (long long)R)};
     if (R <= 32) {
-        DgradArgs g{};
-        g.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
-        g.w.w = W, g.w.co = Co, g.w.ci = Ci;
-        g.prev = make_act(zprev, coef_prev, R, Ci);
-        g.dyprev = dyprev, g.stats = nullptr;
+        DgradArgs g = make_dgrad(make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts), Ci, W, zprev, coef_prev, dyprev, nullptr);
         if (coef_prev) g.bb = bb;
-        WgradArgs wg{};
-        wg.dz = g.dz;
-        wg.prev = make_act(zprev, coef_prev, R, Ci, db ? Ci : -1);
-        wg.ncols = Ci + (db ? 1 : 0);
+        const WgradArgs wg = make_wgrad(g.dz, Ci, zprev, coef_prev, db != nullptr);
         const int tm = (Co + 31) / 32, tn = (wg.ncols + 31) / 32, ntiles = tm * tn;
         const int n_d = (Ci + 31) / 32, n_w = (ntiles + 3) / 4;
         const dim3 grid(n_d + n_w), block(256);
-        const bool pm = coef_prev != nullptr, vec = Co % 64 == 0;
-#define SN_SB(ZM, PM)                                                                                                   \
-    do {                                                                                                                \
-        if (vec)                                                                                                        \
-            hipLaunchKernelGGL((small_bwd_kernel<ZM, PM, true>), grid, block, 0, st, g, wg, dW, db, tn, ntiles, n_d);    \
-        else                                                                                                            \
-            hipLaunchKernelGGL((small_bwd_kernel<ZM, PM, false>), grid, block, 0, st, g, wg, dW, db, tn, ntiles, n_d);   \
-    } while (0)
-        if (dz_mode == DZ_PLAIN) {
-            if (pm) SN_SB(DZ_PLAIN, ACT_BN_RELU); else SN_SB(DZ_PLAIN, ACT_NONE);
-        } else if (dz_mode == DZ_BN) {
-            if (pm) SN_SB(DZ_BN, ACT_BN_RELU); else SN_SB(DZ_BN, ACT_NONE);
-        } else {
-            if (pm) SN_SB(DZ_POOL, ACT_BN_RELU); else SN_SB(DZ_POOL, ACT_NONE);
-        }
-#undef SN_SB
+        dispatch_modes(ZModes<DZ_PLAIN, DZ_BN, DZ_POOL>{}, PModes<ACT_NONE, ACT_BN_RELU>{}, dz_mode, coef_prev != nullptr, Co % 64 == 0,
+                       [&](auto zm, auto pm, auto vec) {
+                           hipLaunchKernelGGL((small_bwd_kernel<decltype(zm)::value, decltype(pm)::value, decltype(vec)::value>), grid, block, 0,
+                                              st, g, wg, dW, db, tn, ntiles, n_d);
+                       });
         SN_LAUNCH_CHECK();
         return 0;
     }
@@ -2477,7 +2418,7 @@ extern "C" int sn_layer_backward(int R, int Ci, int Co, int dz_mode, const float
         SN_REQUIRE(z && (dz_mode != DZ_BN || dy) && (dz_mode != DZ_POOL || (gsel && argsel)), "null pointer");
         const int G = launch_conv_bwd_fused(R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev,
                                             stats, part, st);
-        const int nred = (Co * Ci) % 4 == 0 ? (Co * Ci + kRedElems - 1) / kRedElems : (Co * Ci + 63) / 64;
+        const int nred = wgrad_reduce_blocks(Co * Ci);
         hipLaunchKernelGGL(post_bwd_kernel, dim3(nred + (Ci + kChan - 1) / kChan), dim3(1024), 0, st, nred, G, Co, Ci, part, dW,
                            G, Ci, stats, bb);
         SN_LAUNCH_CHECK();
@@ -2494,8 +2435,7 @@ extern "C" int sn_layer_backward(int R, int Ci, int Co, int dz_mode, const float
         return 0;
     }
     const int nsplit = sn_linear_wgrad_splits(R, Ci, Co, db ? 1 : 0);
-    int rps = (R + nsplit - 1) / nsplit;
-    rps = ((rps + BK - 1) / BK) * BK;
+    const int rps = wgrad_rows_per_split(R, nsplit);
     // the head's top layer above 32 rows (dZ = dY as given, bias gradient wanted): the combined launch as well -- the bias gradient
     // is the column sums of dY, taken by extra workgroups of the closing launch instead of a ones column in the weight-gradient
     // tiles (four launches before: wgrad with the bias column, its reduction, dgrad, BatchNorm coefficients; 30 -> 17 us at 512 rows)
@@ -2513,26 +2453,10 @@ extern "C" int sn_layer_backward(int R, int Ci, int Co, int dz_mode, const float
         SN_LAUNCH_CHECK();
         return 0;
     }
-    DgradArgs d{};
-    d.dz = make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts);
-    d.w.w = W, d.w.co = Co, d.w.ci = Ci;
-    d.prev = make_act(zprev, coef_prev, R, Ci);
-    d.dyprev = dyprev, d.stats = stats;
-    WgradArgs w{};
-    w.dz = d.dz;
-    w.prev = make_act(zprev, coef_prev, R, Ci, -1);
-    w.ncols = Ci, w.part = part, w.rows_per_split = rps;
-    const int wgx = Co / TileW::BM, wgy = Ci / TileW::BN, n_w = wgx * wgy * nsplit;
-    const int dgx = R / TileBig::BM, n_d = dgx * (Ci / TileBig::BN);
-    const dim3 grid(n_w + n_d);
-    const size_t lds = shaped_lds(std::max(lds_bytes<TileBig>(), lds_bytes<TileW>()), grid);
-    if (dz_mode == DZ_BN)
-        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, DZ_BN, ACT_BN_RELU>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w, wgx, wgy, dgx);
-    else if (dz_mode == DZ_POOL)
-        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, DZ_POOL, ACT_BN_RELU>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w, wgx, wgy, dgx);
-    else
-        hipLaunchKernelGGL((linear_bwd_kernel<TileBig, DZ_PLAIN, ACT_BN_RELU>), grid, dim3(TileBig::THREADS), lds, st, d, w, n_w, wgx, wgy, dgx);
-    const int nred = (Co * Ci) % 4 == 0 ? (Co * Ci + kRedElems - 1) / kRedElems : (Co * Ci + 63) / 64;
+    // (fast: plain dZ too -- the head's top layer, plain_top)
+    const int dgx = launch_linear_bwd(ZModes<DZ_PLAIN, DZ_BN, DZ_POOL>{}, make_dz(dz_mode, dy, z, kcoef, gsel, argsel, R, Co, npts), Ci, W, zprev,
+                                      coef_prev, dyprev, stats, part, nsplit, rps, st);
+    const int nred = wgrad_reduce_blocks(Co * Ci);
     const int ndb = db ? (Co + 63) / 64 : 0;
     // (the statistics partials THIS route fills: one per TileBig row block -- at R == 64 sn_linear_stats_blocks counts TileSmall
     //  blocks, and summing that many read an unwritten block: wrong dgamma / dbeta / dbias of the layer below at exactly 64 rows)
@@ -2560,39 +2484,27 @@ static void launch_conv_bwd_in3(int R, const float *dy, const float *z, const fl
     ConvBwdArgs a{};
     a.w_in = w_in, a.b_in = b_in;  // (zprev == NULL: the xyz layer's parameters, Zprev is rebuilt from x_in)
     if (fx) a.acc_in = fx->acc_in, a.bb_in = fx->bb_in, a.acc_out = nullptr, a.zero_ptr = fx->zero_ptr, a.zero_n = fx->zero_n;
-    a.dz.mode = DZ_BN, a.dz.dy = dy, a.dz.z = z, a.dz.rows = R, a.dz.ch = Co, a.dz.npts = 1;
-    a.dz.k1 = kcoef, a.dz.k2 = kcoef ? kcoef + Co : nullptr, a.dz.k3 = kcoef ? kcoef + 2 * Co : nullptr;
+    a.dz = make_dz(DZ_BN, dy, z, kcoef, nullptr, nullptr, R, Co, 1);
     a.W = W, a.zprev = zprev, a.scale_prev = coef_prev, a.shift_prev = coef_prev + Ci;
     a.dyprev = nullptr, a.stats = stats, a.part = part, a.xin = x_in;  // dYprev is not materialised: nothing reads it
     constexpr int TR = CbfShape<64, 64>::TR;
     static_assert(TR == CbxShape<64, 64>::TR, "same tiling in both kernels");
     a.ntiles = (R + TR - 1) / TR;
     const int G = conv_bwd_fused_groups(R);
+    const dim3 grid(G), block(512);
+    const bool fullr = R % TR == 0;
 #if SN_BF16X3
-#define SN_CBF_IN3 conv_bwd_bx3_kernel
     constexpr size_t lds = CbxShape<64, 64>::LDS_BYTES_IN3;
-    if (!zprev) {  // Zprev rebuilt from the cloud (the forward did not materialise it)
-        static SnLdsAttr rt, rf;
-        (void)sn_lds_attr(rt, (const void *)conv_bwd_bx3_kernel<64, 64, DZ_BN, true, true, true>, lds, "conv_bwd_bx3_kernel");
-        (void)sn_lds_attr(rf, (const void *)conv_bwd_bx3_kernel<64, 64, DZ_BN, false, true, true>, lds, "conv_bwd_bx3_kernel");
-        if (R % TR == 0)
-            hipLaunchKernelGGL((conv_bwd_bx3_kernel<64, 64, DZ_BN, true, true, true>), dim3(G), dim3(512), lds, st, a);
-        else
-            hipLaunchKernelGGL((conv_bwd_bx3_kernel<64, 64, DZ_BN, false, true, true>), dim3(G), dim3(512), lds, st, a);
-        return;
-    }
-#else
-#define SN_CBF_IN3 conv_bwd_fused_kernel
-    constexpr size_t lds = CbfShape<64, 64>::LDS_BYTES_IN3;
-#endif
-    static SnLdsAttr at, af;
-    (void)sn_lds_attr(at, (const void *)SN_CBF_IN3<64, 64, DZ_BN, true, true>, lds, "conv_bwd (xyz layer below)");
-    (void)sn_lds_attr(af, (const void *)SN_CBF_IN3<64, 64, DZ_BN, false, true>, lds, "conv_bwd (xyz layer below)");
-    if (R % TR == 0)
-        hipLaunchKernelGGL((SN_CBF_IN3<64, 64, DZ_BN, true, true>), dim3(G), dim3(512), lds, st, a);
+    if (!zprev)  // Zprev rebuilt from the cloud (the forward did not materialise it)
+        launch_lds_twins<conv_bwd_bx3_kernel<64, 64, DZ_BN, true, true, true>, conv_bwd_bx3_kernel<64, 64, DZ_BN, false, true, true>>(
+            fullr, grid, block, lds, "conv_bwd_bx3_kernel", st, a);
     else
-        hipLaunchKernelGGL((SN_CBF_IN3<64, 64, DZ_BN, false, true>), dim3(G), dim3(512), lds, st, a);
-#undef SN_CBF_IN3
+        launch_lds_twins<conv_bwd_bx3_kernel<64, 64, DZ_BN, true, true>, conv_bwd_bx3_kernel<64, 64, DZ_BN, false, true>>(
+            fullr, grid, block, lds, "conv_bwd (xyz layer below)", st, a);
+#else
+    launch_lds_twins<conv_bwd_fused_kernel<64, 64, DZ_BN, true, true>, conv_bwd_fused_kernel<64, 64, DZ_BN, false, true>>(
+        fullr, grid, block, CbfShape<64, 64>::LDS_BYTES_IN3, "conv_bwd (xyz layer below)", st, a);
+#endif
 }
 
 extern "C" int sn_layer_backward_in3(int R, int Ci, int Co, const float *dy, const float *z, const float *kcoef, const float *W,
@@ -2607,7 +2519,7 @@ extern "C" int sn_layer_backward_in3(int R, int Ci, int Co, const float *dy, con
     launch_conv_bwd_in3(R, dy, z, kcoef, W, zprev, coef_prev, stats, part, x_in, st);
     const int G = conv_bwd_fused_groups(R);
     const BnBwd bb{coef_prev, prev_dgamma, prev_dbeta, prev_dbias, prev_kcoef, (long long)R};
-    const int nred = (Co * Ci + kRedElems - 1) / kRedElems;
+    const int nred = wgrad_reduce_blocks(Co * Ci);
     hipLaunchKernelGGL(post_bwd_in3_kernel, dim3(nred + (Ci + kChan - 1) / kChan), dim3(1024), 0, st, nred, G, Co, Ci, part, dW, G,
                        Ci, stats, bb, W_in, b_in, dW_in, MultiRed{}, StepTail{});
     SN_LAUNCH_CHECK();
@@ -2693,7 +2605,7 @@ extern "C" int sn_conv_stack_backward(int B, int N, int nlayers, const int *chan
     int nb = 0;
     for (int l = 1; l < nlayers; ++l) {
         mr.first[l - 1] = nb, mr.part[l - 1] = part[l], mr.dW[l - 1] = dW[l], mr.elems[l - 1] = ch[l] * ch[l + 1];
-        nb += (ch[l] * ch[l + 1] + kRedElems - 1) / kRedElems;
+        nb += wgrad_reduce_blocks(ch[l] * ch[l + 1]);
     }
     mr.first[nlayers - 1] = nb;
     mr.zero_ptr = accb(1), mr.zero_n = kFxLayer;

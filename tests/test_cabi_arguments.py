@@ -5,7 +5,7 @@ any device work.  So do the entries of include/samplenet_hip_internal.h that the
 (sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
 transforms, the orthogonality regulariser and sn_bn_relu_*, and the nine entries of the one-batch task evaluation (cyclic padding, the
 valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped), and the twelve entries of the sampler
-step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device), and the ten per-layer entries of the PointNet MLP (tests/test_gpu_mlp.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 import json
@@ -172,9 +172,44 @@ FC_CHAIN = {
                                  [2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 19, 20, 23, 24], [10, 11, 12, 14, 15, 17, 19]),
 }
 
+# The ten per-layer entries of the PointNet MLP (csrc/pointnet_mlp.hip, csrc/pointnet_mlp_backward.hip), same rules as ENTRIES: every
+# size is >= 1 (0 is refused like -1), dz_mode is 0 (plain), 1 (BatchNorm) or 2 (pool).  The bases sit on the route whose refusals the
+# cases past the generic ones name (_mlp_cases()): 64 rows for the tile kernels, 128 / 256 aligned rows for the fused conv entries.
+MLP = {
+    # R, Ci, Co, ain, coef_prev, W, bias, z, stats, stream
+    "sn_linear_forward": ([64, 8, 8, Pp, None, Pp, None, Pp, None, None], [0, 1, 2], [3, 5, 7]),
+    # R, Ci, Co, ain, coef_prev, W, bias, z, stream
+    "sn_linear_forward_rows": ([64, 8, 8, Pp, None, Pp, None, Pp, None], [0, 1, 2], [3, 5, 7]),
+    # R, Ci, Co, ain, coef_prev, W, bias, z, stats, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, coef, stream
+    "sn_layer_forward_bn": ([64, 8, 8, Pp, None, Pp, None, Pp, Pp, Pp, Pp, 1e-5, 0.1, None, None, None, Pp, None], [0, 1, 2],
+                            [3, 5, 7, 8, 9, 10, 16]),
+    # R, Ci, Co, npts, ain, coef_prev, W, bias, z, stats, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, coef,
+    # pool_val, pool_idx, pooled, argsel, zsel, stream
+    "sn_conv_forward_bn_pool": ([128, 64, 64, 64, Pp, Pp, Pp, None, Pp, Pp, Pp, Pp, 1e-5, 0.1, None, None, None, Pp, Pp, Pp, Pp, Pp, Pp, None],
+                                [0, 1, 2, 3], [4, 5, 6, 8, 9, 10, 11, 17, 18, 19, 20, 21, 22]),
+    # R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev, stats, stream
+    "sn_linear_dgrad": ([64, 8, 8, 0, Pp, None, None, None, None, 1, Pp, Pp, None, Pp, None, None], [0, 1, 2], [10, 13]),
+    # R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, aprev, coef_prev, part, dW, db, stream
+    "sn_linear_wgrad": ([64, 8, 8, 0, Pp, None, None, None, None, 1, Pp, None, Pp, Pp, None, None], [0, 1, 2], [10, 12, 13]),
+    # R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev, stats, part, stream
+    "sn_conv_backward_partials": ([256, 64, 64, 1, Pp, Pp, Pp, None, None, 64, Pp, Pp, Pp, Pp, Pp, Pp, None], [0, 1, 2],
+                                  [4, 5, 6, 10, 11, 12, 13, 14, 15]),
+    # R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev, stats, part, dW, stream
+    "sn_linear_backward": ([64, 8, 8, 0, Pp, None, None, None, None, 1, Pp, Pp, None, Pp, None, Pp, Pp, None], [0, 1, 2], [10, 11, 13, 15, 16]),
+    # R, Ci, Co, dz_mode, dy, z, kcoef, gsel, argsel, npts, W, zprev, coef_prev, dyprev, stats, part, dW, db, prev_dgamma, prev_dbeta,
+    # prev_dbias, prev_kcoef, prev_bn_rows, stream
+    "sn_layer_backward": ([64, 8, 8, 0, Pp, None, None, None, None, 1, Pp, Pp, None, Pp, None, Pp, Pp, None, None, None, None, None, 0, None],
+                          [0, 1, 2], [10, 11, 13, 16]),
+    # R, Ci, Co, dy, z, kcoef, W, zprev, coef_prev, stats, part, dW, prev_dgamma, prev_dbeta, prev_dbias, prev_kcoef, x_in, W_in, b_in, dW_in,
+    # stream
+    "sn_layer_backward_in3": ([256, 64, 64, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, None, Pp, Pp, Pp, None, Pp, None], [0, 1, 2],
+                              [3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16, 17, 19]),
+}
+
 
 def _with(name, changes):
-    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY.get(name) or FC_CHAIN[name])[0])
+    args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY.get(name) or FC_CHAIN.get(name)
+                 or MLP[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -238,7 +273,7 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
-    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases() + _fc_chain_cases()
+    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases() + _fc_chain_cases() + _mlp_cases()
 
 
 def _skinny_cases():
@@ -382,6 +417,46 @@ def _fc_chain_cases():
     return out
 
 
+def _mlp_cases():
+    out = []
+    add = lambda cid, name, ch, text=None, code=BAD: out.append(("%s-%s" % (name, cid), name, _with(name, ch), code, text or name))
+    for name, (base, sizes, required) in MLP.items():
+        for pos in sizes:
+            add("size%d-negative" % pos, name, {pos: -1})
+            add("size%d-zero" % pos, name, {pos: 0})
+        for pos in required:
+            add("arg%d-null" % pos, name, {pos: None})
+    for name in ("sn_linear_dgrad", "sn_linear_wgrad", "sn_linear_backward", "sn_layer_backward"):
+        for bad in (-1, 3):
+            add("dz_mode-is-%d" % bad, name, {3: bad}, "bad dz_mode")
+    cp, lb = "sn_conv_backward_partials", "sn_layer_backward"
+    for bad in (-1, 0, 3):  # (the fused kernel serves the BatchNorm and the pool form only)
+        add("dz_mode-is-%d" % bad, cp, {3: bad}, "bad dz_mode")
+    add("pool-without-gsel", cp, {3: 2, 8: Pp}, "missing gradient source")
+    add("pool-without-argsel", cp, {3: 2, 7: Pp}, "missing gradient source")
+    # shapes the fused backward kernel does not serve: fewer than 256 rows, other channel counts, a pool over clouds that are no
+    # multiple of 64 points
+    for cid, ch in (("R-255", {0: 255}), ("R-64", {0: 64}), ("Ci-192", {1: 192}), ("Ci-128-Co-64", {1: 128}), ("Co-40", {2: 40}),
+                    ("pool-npts-48", {3: 2, 7: Pp, 8: Pp, 9: 48}), ("pool-npts-0", {3: 2, 7: Pp, 8: Pp, 9: 0})):
+        add(cid, cp, ch, "shape not served by the fused kernel", UNSUP)
+    fp = "sn_conv_forward_bn_pool"
+    for cid, ch in (("R-64", {0: 64}), ("R-130", {0: 130}), ("npts-32", {3: 32}), ("npts-96", {0: 192, 3: 96}), ("R-no-multiple-of-npts", {0: 192, 3: 128}),
+                    ("Co-96", {2: 96}), ("Ci-40", {1: 40})):
+        add(cid, fp, ch, "needs 64-aligned rows / points / channels", UNSUP)
+    # the layer below has a BatchNorm (coef_prev): its outputs are required, the statistics scratch above 32 rows only
+    with_bn = {12: Pp, 14: Pp, 18: Pp, 19: Pp, 21: Pp}
+    for cid, pos in (("prev_dgamma", 18), ("prev_dbeta", 19), ("prev_kcoef", 21), ("stats", 14)):
+        add("coef_prev-without-" + cid, lb, {**with_bn, pos: None}, "previous-layer BatchNorm outputs missing")
+    add("coef_prev-without-prev_dgamma-at-32-rows", lb, {**with_bn, 0: 32, 14: None, 18: None}, "previous-layer BatchNorm outputs missing")
+    add("prev_bn_rows-at-33-rows", lb, {0: 33, 22: 5}, "prev_bn_rows > 0")
+    add("prev_bn_rows-at-64-rows-with-coef_prev", lb, {**with_bn, 22: 4096}, "prev_bn_rows > 0")
+    add("no-scratch-above-32-rows", lb, {0: 33, 15: None}, "scratch missing")
+    in3 = "sn_layer_backward_in3"
+    for cid, ch in (("R-255", {0: 255}), ("Ci-128", {1: 128}), ("Co-128", {2: 128})):
+        add(cid, in3, ch, "shape not supported by the input-layer variant")
+    return out
+
+
 def _transform_cases(nulled):
     out = []
     tf, tb, of, ob = "sn_cloud_transform_forward", "sn_cloud_transform_backward", "sn_orthogonality_loss_forward", "sn_orthogonality_loss_backward"
@@ -408,7 +483,7 @@ def _transform_cases(nulled):
 
 
 CASES = _cases()
-IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + sorted(FC_CHAIN) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
+IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + sorted(FC_CHAIN) + sorted(MLP) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
                                                "sn_skinny_linear_scratch_bytes"]
 
 _CHILD = r"""
@@ -447,7 +522,7 @@ def results():
 def test_the_table_walks_every_entry_in_scope():
     from samplenet_amd import _lib
 
-    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()) + list(STEP_LOSS.items()):
+    for name, (base, sizes, required) in list(ENTRIES.items()) + list(INTERNAL.items()) + list(TASK_BATCH.items()) + list(STEP_LOSS.items()) + list(MLP.items()):
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto), name
         for pos, ty in enumerate(proto):
