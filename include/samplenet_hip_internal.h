@@ -615,6 +615,29 @@ long long sn_adam_state_bytes(void);
 int sn_adam_update(int nchunks, const void *chunks, float *exp_avg, float *exp_avg_sq, void *state, double beta1, double beta2,
                    double eps, double weight_decay, double grad_scale, int tf_epsilon, sn_stream_t stream);
 
+/* The two other optimizers of registration/main.py:166-171 as ONE launch each: torch.optim.SGD (momentum, dampening, Nesterov; also
+ * classification/train_classifier.py:133 tf.train.MomentumOptimizer) and torch.optim.RMSprop (not centered).  Replace no reference C
+ * interface.  Chunk table, NULL-gradient rule, alignment rules and the 64-byte state block are sn_adam_update's: word 0 lr, word 3 t,
+ * word 4 the arrival counter (zero between launches); words 1 and 2 are neither read nor written.  The last workgroup to arrive writes
+ * t + 1 and clears the counter, so a captured launch replays as it is.
+ *   momentum_buf   flat fp32 buffer addressed by the table's moment_offset, 16-byte aligned; NULL exactly when momentum == 0 (then
+ *                  no buffer is read or written)
+ *   square_avg     (RMSprop) flat fp32 buffer, 16-byte aligned, distinct from momentum_buf
+ *   per element (fp32, g1 alone formed in fp64 and rounded once; operation order pinned in csrc/optimizer.hip):
+ *            g1 = grad * grad_scale + weight_decay * p
+ *     SGD:   momentum != 0: b' = g1 when t == 0 (torch's first step: the buffer is a copy of the gradient, dampening ignored), else
+ *            b' = momentum b + (1 - dampening) g1;  d = nesterov ? g1 + momentum b' : b';  momentum == 0: d = g1;  p' = p - lr d.
+ *            t is ONE count per launch, i.e. per parameter group: it differs from torch's per-parameter "buffer is None" only for a
+ *            parameter whose gradient was NULL in the group's first step, and only when dampening != 0.
+ *     RMSprop: s' = alpha s + (1 - alpha) g1^2;  q = g1 / (sqrt(s') + eps);  momentum == 0: p' = p - lr q;
+ *            else b' = momentum b + q, p' = p - lr b'.
+ * Checked before any launch: nchunks >= 0; momentum, dampening, eps, weight_decay >= 0; 0 <= alpha < 1; nesterov needs momentum > 0
+ * and dampening == 0; non-null, aligned table / block / buffers.  nchunks == 0 is a no-op that succeeds (the block is not touched). */
+int sn_sgd_update(int nchunks, const void *chunks, float *momentum_buf, void *state, double momentum, double dampening,
+                  double weight_decay, double grad_scale, int nesterov, sn_stream_t stream);
+int sn_rmsprop_update(int nchunks, const void *chunks, float *square_avg, float *momentum_buf, void *state, double alpha, double eps,
+                      double weight_decay, double momentum, double grad_scale, sn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * Training batches assembled ON THE DEVICE from an HBM-resident dataset in ONE launch (samplenet_amd/device_data.py; the reference's
  * data side: registration/data/modelnet_loader_torch.py:114-125 ModelNetCls.__getitem__, src/pctransforms.py, src/qdataset.py:133-179

@@ -166,6 +166,9 @@ PROTOTYPES = {
     "sn_adam_state_bytes": [],
     "sn_adam_update": [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                        ctypes.c_double, _i, _vp],
+    "sn_sgd_update": [_i, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _vp],
+    "sn_rmsprop_update": [_i, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                          ctypes.c_double, _vp],
     "sn_pose_error_forward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_pose_error_backward": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_chamfer_mean_per_cloud": [_i, _i, _i, _vp, _vp, _vp, _vp],

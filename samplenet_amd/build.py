@@ -37,7 +37,7 @@ SOURCES = [
     ("fc_chain.hip", []),
     ("task_network.hip", []),
     ("cloud_transform.hip", []),
-    # the Adam update's operation order is pinned (a rounding bound is derived from it): only the fmaf's it writes out
+    # the Adam / SGD / RMSprop updates' operation order is pinned (rounding bounds are derived from it): only the fmaf's written out
     ("optimizer.hip", ["-ffp-contract=off"]),
     # the batch assembly's fp32 operation order is its contract (include/samplenet_hip_internal.h; tests/batch_ref.py counts it)
     ("batch_assemble.hip", ["-ffp-contract=off"]),

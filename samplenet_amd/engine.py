@@ -36,16 +36,16 @@ class SamplerTrainStep:
         self.x1 = self.igt = None
         if task_loss_igt and not (input_source is not None and input_source.makes_pairs and task_loss is not None):
             raise ValueError("task_loss_igt needs a task_loss and an input_source that makes pairs")
-        # optimizer: a samplenet_amd.optim.Adam over the net's parameters -- its update (one launch per parameter group) is issued
-        # right behind reducer.reduce(): as the last node(s) of the step's graph where the gradients are final inside it (no
+        # optimizer: a samplenet_amd.optim.Adam, SGD or RMSprop over the net's parameters (everything below goes through their shared
+        # base) -- its update (one launch per parameter group) is issued right behind reducer.reduce(): as the last node(s) of the step's graph where the gradients are final inside it (no
         # collective, or allreduce 'graph' / 'graph-fork'), behind the Python-side collective otherwise ('after', the split step),
         # eagerly when use_graph=False.  The graph must see one fixed set of gradient addresses: a reducer is required.
         if optimizer is not None:
-            from .optim import Adam
+            from .optim import _OneLaunchOptimizer
 
-            if not isinstance(optimizer, Adam):
-                raise TypeError("optimizer: a samplenet_amd.optim.Adam (got %s); step any other optimizer yourself behind the call"
-                                % type(optimizer).__name__)
+            if not isinstance(optimizer, _OneLaunchOptimizer):
+                raise TypeError("optimizer: a samplenet_amd.optim.Adam, SGD or RMSprop (got %s.%s); step any other optimizer yourself "
+                                "behind the call" % (type(optimizer).__module__, type(optimizer).__name__))
             if reducer is None:
                 raise ValueError("optimizer= needs a gradient sink (FlatGradAllReducer): the update reads one fixed set of .grad tensors")
         self.optimizer = optimizer
