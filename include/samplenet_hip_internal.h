@@ -735,6 +735,50 @@ int sn_batch_assemble(int B, int N, int P, int L, int repeat, const float *point
                       const float *pair_quat, int layout, float *p0, float *p1, long long *out_labels, float *igt, int *items,
                       sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Ball-query neighbourhoods and the fused query-and-group of a PointNet++ set abstraction (csrc/ball_query.hip; restated in numpy
+ * float32 by tests/ball_ref.py).  For query j and dataset point k, all fp32, every operation rounded once, nothing contracted:
+ *     dx = x_query - x_dataset, dy, dz likewise;   d2 = ((dx*dx) + (dy*dy)) + (dz*dz)
+ *     SN_BALL_RULE_SQRT     pass = max(sqrtf(d2), 1e-20f) < radius, sqrtf correctly rounded: the reference's rule
+ *                           (classification/grouping/tf_grouping_g.cu:24-25, test/query_ball_point.cpp:32-33);
+ *     SN_BALL_RULE_SQUARED  pass = d2 < fl(radius * radius): the rule of Pointnet2_PyTorch's ball_query AS RECALLED -- its source
+ *                           is not at hand, so this rule is UNPINNED (like knn_cuda's tie order).
+ * The rules differ only for pairs at the boundary.  Any float radius is legal: a NaN or a radius <= 0 gives all-empty rows under
+ * both rules, and under the reference's rule so does every radius <= 1e-20f.  A NaN distance never passes.
+ * Row j of idx holds the FIRST nsample passing dataset indices in ascending order; with 0 < cnt < nsample hits, slots cnt ..
+ * nsample-1 repeat the first hit; pts_cnt[j] = min(hits, nsample).  DEVIATION: a row with no hit is written as zeros with
+ * pts_cnt[j] = 0 -- the reference leaves such a row unwritten (whatever the buffer held).  nsample has no upper bound.
+ * One launch, no workspace, no atomics, deterministic, capturable.  Checked on the host before any device work: a negative size,
+ * nsample < 1, an unknown rule / layout / use_xyz, a NULL required pointer, n == 0 with b * m > 0 -> SN_ERR_BAD_ARGUMENT; b == 0
+ * or m == 0 is a no-op that succeeds; a launch of more than 2^31 - 1 workgroups (b * m beyond 3e10) -> SN_ERR_UNSUPPORTED. */
+#define SN_BALL_RULE_SQRT 0
+#define SN_BALL_RULE_SQUARED 1
+/* query_ball_point_gpu + queryBallPointLauncher (tf_grouping_g.cu:3-36, 125-128; op shell tf_grouping.cpp:66-100; Python
+ * tf_grouping.py:13-28).  xyz1: the dataset, (b,n,3) [SN_LAYOUT_BNC] or (b,3,n) [SN_LAYOUT_BCN] by layout1; xyz2: the queries,
+ * (b,m,3) or (b,3,m) by layout2; idx (b,m,nsample) int32; pts_cnt (b,m) int32, may be NULL. */
+int sn_ball_query(int b, int n, int m, float radius, int nsample, int rule, const float *xyz1, int layout1, const float *xyz2,
+                  int layout2, int *idx, int *pts_cnt, sn_stream_t stream);
+/* QueryAndGroup in ONE launch (replaces query_ball_point_gpu + group_point_gpu, tf_grouping_g.cu:3-36, 40-57, and the centre
+ * subtraction of the set-abstraction layer around them; Pointnet2_PyTorch's QueryAndGroup.forward).  xyz (b,n,3), new_xyz (b,m,3),
+ * features (b,c,n) or NULL with c == 0; out (b, 3 use_xyz + c, m, nsample) channel-major: with use_xyz, channels 0..2 are
+ * xyz[idx] - new_xyz[j] (one exact fp32 subtraction each), the remaining c channels are features[:, :, idx].  idx / pts_cnt are
+ * written exactly as by sn_ball_query (pts_cnt may be NULL); an empty ball therefore groups point 0.  c == 0 without use_xyz ->
+ * SN_ERR_BAD_ARGUMENT.  Bit-identical to sn_ball_query + sn_grouping_operation + the subtraction. */
+int sn_ball_group_forward(int b, int n, int m, int c, float radius, int nsample, int rule, int use_xyz, const float *xyz,
+                          const float *new_xyz, const float *features, int *idx, int *pts_cnt, float *out, sn_stream_t stream);
+/* Its gradient (replaces group_point_grad_gpu, tf_grouping_g.cu:61-78, for both gathered tensors, plus the centre's term).
+ * grad_out (b, 3 use_xyz + c, m, nsample) is read where it lies (no slice is copied).  Each output may be NULL; one that is NULL is
+ * not touched:
+ *   grad_features (b,c,n), grad_xyz (b,n,3): OVERWRITTEN (the caller zeroes nothing), summed with float atomics, so the last bits
+ *       depend on arrival order (the contract of sn_grouping_operation_grad's atomic route).  n <= 16384: a workgroup accumulates up
+ *       to 16 channels of one cloud as dense rows in LDS (LDS atomics) and stores them; beyond: zero-filled inside, then global
+ *       float atomics.  An index outside [0,n) adds to nothing;
+ *   grad_new_xyz (b,m,3): grad_new_xyz[b,j,:] = -(sum over s of grad_out[b,0:3,j,s]) in ONE order: lane l of a wave adds slots
+ *       s = l, l + 64, .. ascending, the 64 lane sums meet by the xor tree (offsets 32, 16, .. 1), one negation: bit-reproducible.
+ * Without use_xyz the two point gradients are zeros.  idx / grad_out may be NULL when m == 0 (the zero-fill still happens). */
+int sn_ball_group_backward(int b, int n, int m, int c, int nsample, int use_xyz, const int *idx, const float *grad_out,
+                           float *grad_features, float *grad_xyz, float *grad_new_xyz, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,9 @@ PROTOTYPES = {
     "sn_batch_state_bytes": [],
     "sn_batch_assemble": [_i, _i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _i, _i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp,
                           _vp, _vp, _vp, _vp],
+    "sn_ball_query": [_i, _i, _i, _f, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
+    "sn_ball_group_forward": [_i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_ball_group_backward": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"sn_last_error_string": ctypes.c_char_p, "sn_workspace_bytes": ctypes.c_longlong,
              "sn_pairscan_workspace_bytes": ctypes.c_longlong, "sn_linear_forward_maxpool_wide_scratch_bytes": ctypes.c_longlong,

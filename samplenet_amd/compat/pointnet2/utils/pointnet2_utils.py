@@ -1,10 +1,20 @@
-"""The functions of Pointnet2_PyTorch's pointnet2_utils that the reference calls, on the kernels of libsamplenet_hip.so:
+"""The functions of Pointnet2_PyTorch's pointnet2_utils that the reference calls, and the grouping half of that module a
+PointNet++-style task network imports beside them, on the kernels of libsamplenet_hip.so:
 
     grouping_operation(features (B,C,N), idx (B,npoint,nsample) int32) -> (B,C,npoint,nsample)   soft_projection.py:8,86,88
     furthest_point_sample(xyz (B,N,3), npoint) -> idx (B,npoint) int32, no gradient             fps.py:4,35
     gather_operation(features (B,C,N), idx (B,npoint) int32) -> (B,C,npoint)                    fps.py:5,39; random_sampling.py:4,42
+    ball_query(radius, nsample, xyz (B,N,3), new_xyz (B,npoint,3)) -> idx (B,npoint,nsample) int32, no gradient
+    QueryAndGroup(radius, nsample, use_xyz=True)(xyz, new_xyz, features (B,C,N) or None) -> (B,3+C,npoint,nsample)
+    GroupAll(use_xyz=True)(xyz, new_xyz, features (B,C,N) or None) -> (B,3+C,1,N)
 
-grouping_operation and gather_operation are differentiable w.r.t. features."""
+grouping_operation and gather_operation are differentiable w.r.t. features; QueryAndGroup w.r.t. features, xyz and new_xyz.
+ball_query and QueryAndGroup compare d2 < radius^2 (ops' "squared" rule: that module's comparison as recalled, its source not being
+at hand -- the reference's own TF op, ops.query_ball_point, compares sqrt(d2) < radius; the two differ only on the boundary).  A
+ball with no point in it gives a row of zeros here (point 0 is grouped); short rows repeat their first hit."""
+import torch
+from torch import nn
+
 from .... import ops
 
 
@@ -18,3 +28,35 @@ def furthest_point_sample(xyz, npoint):
 
 def gather_operation(features, idx):
     return ops.gather_operation(features, idx)
+
+
+def ball_query(radius, nsample, xyz, new_xyz):
+    return ops.ball_query(radius, nsample, xyz, new_xyz, rule="squared", layout=ops.BNC)[0]
+
+
+class QueryAndGroup(nn.Module):
+    """Groups the points of every ball: one launch forward (ops.ball_group)."""
+
+    def __init__(self, radius, nsample, use_xyz=True):
+        super().__init__()
+        self.radius, self.nsample, self.use_xyz = radius, nsample, use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        if features is None and not self.use_xyz:
+            raise ValueError("Cannot have not features and not use xyz as a feature!")
+        return ops.ball_group(self.radius, self.nsample, xyz, new_xyz, features, use_xyz=self.use_xyz, rule="squared")
+
+
+class GroupAll(nn.Module):
+    """One group holding the whole cloud (plain tensor ops: a transpose and a concatenation)."""
+
+    def __init__(self, use_xyz=True):
+        super().__init__()
+        self.use_xyz = use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        grouped_xyz = xyz.transpose(1, 2).unsqueeze(2)  # (B,3,1,N)
+        if features is None:
+            return grouped_xyz
+        grouped_features = features.unsqueeze(2)        # (B,C,1,N)
+        return torch.cat([grouped_xyz, grouped_features], dim=1) if self.use_xyz else grouped_features

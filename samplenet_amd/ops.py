@@ -520,6 +520,102 @@ def gather_operation(features, idx):
     return GroupingOperationFunction.apply(features, idx.unsqueeze(-1)).squeeze(-1)
 
 
+# --------------------------------------------------------------------------------------------- ball query
+BALL_RULES = {"sqrt": 0, "squared": 1}  # SN_BALL_RULE_*
+
+
+def _ball_rule(rule):
+    if rule not in BALL_RULES:
+        raise ValueError("ball query rule must be 'sqrt' or 'squared', got %r" % (rule,))
+    return BALL_RULES[rule]
+
+
+def ball_query(radius, nsample, xyz, new_xyz, rule="sqrt", layout=BNC, xyz_layout=None):
+    """Radius neighbourhoods (no gradient): the FIRST nsample points of `xyz` (ascending index) inside the ball of every point of
+    `new_xyz`; short rows repeat their first hit, an empty ball gives a row of zeros with count 0 (sn_ball_query).
+
+    new_xyz (B,M,3) [BNC] or (B,3,M) [BCN] by `layout`; xyz (B,N,3) or (B,3,N) by `xyz_layout` (default: `layout`).
+    rule "sqrt": max(sqrt(d2), 1e-20) < radius, the reference's; "squared": d2 < radius * radius (unpinned).
+    Returns idx (B,M,nsample) int32 and pts_cnt (B,M) int32."""
+    rule = _ball_rule(rule)
+    _need_gpu(xyz, new_xyz)
+    xyz_layout = layout if xyz_layout is None else xyz_layout
+    xyz, new_xyz = _f32c(xyz.detach()), _f32c(new_xyz.detach())
+    for t, lay, name in ((xyz, xyz_layout, "xyz"), (new_xyz, layout, "new_xyz")):
+        if t.dim() != 3 or t.shape[2 if lay == BNC else 1] != 3:
+            raise ValueError("ball_query: %s must be (B,N,3) for BNC or (B,3,N) for BCN, got %s" % (name, tuple(t.shape)))
+    B = xyz.shape[0]
+    N = xyz.shape[1] if xyz_layout == BNC else xyz.shape[2]
+    M = new_xyz.shape[1] if layout == BNC else new_xyz.shape[2]
+    idx = torch.empty(B, M, nsample, device=xyz.device, dtype=torch.int32)
+    cnt = torch.empty(B, M, device=xyz.device, dtype=torch.int32)
+    with torch.cuda.device(xyz.device):
+        check(lib.sn_ball_query(B, N, M, float(radius), nsample, rule, ptr(xyz), xyz_layout, ptr(new_xyz), layout, ptr(idx), ptr(cnt),
+                                _stream(xyz)), "sn_ball_query")
+    return idx, cnt
+
+
+def query_ball_point(radius, nsample, xyz1, xyz2):
+    """The TF op of classification/grouping/tf_grouping.py:13-28: xyz1 (B,N,3) dataset, xyz2 (B,M,3) queries ->
+    (idx (B,M,nsample) int32, pts_cnt (B,M) int32), the reference's comparison (rule "sqrt")."""
+    return ball_query(radius, nsample, xyz1, xyz2, rule="sqrt", layout=BNC)
+
+
+class BallGroupFunction(torch.autograd.Function):
+    """xyz (B,N,3), new_xyz (B,M,3), features (B,C,N) or None -> out (B, 3 use_xyz + C, M, nsample), idx, pts_cnt: the ball query,
+    the two gathers and the centre subtraction in one launch (sn_ball_group_forward); sn_ball_group_backward gives the three gradients."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, features, radius, nsample, use_xyz, rule):
+        _need_gpu(xyz, new_xyz, features)
+        xyz, new_xyz = _f32c(xyz), _f32c(new_xyz)
+        features = None if features is None else _f32c(features)
+        if xyz.dim() != 3 or xyz.shape[2] != 3 or new_xyz.dim() != 3 or new_xyz.shape[2] != 3:
+            raise ValueError("ball_group: xyz must be (B,N,3) and new_xyz (B,M,3)")
+        b, n, _ = xyz.shape
+        m = new_xyz.shape[1]
+        c = 0 if features is None else features.shape[1]
+        if features is not None and (features.dim() != 3 or features.shape[0] != b or features.shape[2] != n):
+            raise ValueError("ball_group: features must be (B,C,N)")
+        u = 1 if use_xyz else 0
+        out = torch.empty(b, 3 * u + c, m, nsample, device=xyz.device, dtype=torch.float32)
+        idx = torch.empty(b, m, nsample, device=xyz.device, dtype=torch.int32)
+        cnt = torch.empty(b, m, device=xyz.device, dtype=torch.int32)
+        with torch.cuda.device(xyz.device):
+            check(lib.sn_ball_group_forward(b, n, m, c, float(radius), nsample, rule, u, ptr(xyz), ptr(new_xyz), ptr(features), ptr(idx),
+                                            ptr(cnt), ptr(out), _stream(xyz)), "sn_ball_group_forward")
+        ctx.save_for_backward(idx)
+        ctx.dims = (b, n, m, c, nsample, u)
+        ctx.mark_non_differentiable(idx, cnt)
+        return out, idx, cnt
+
+    @staticmethod
+    def backward(ctx, grad_out, _gi, _gc):
+        (idx,) = ctx.saved_tensors
+        b, n, m, c, ns, u = ctx.dims
+        grad_out = _f32c(grad_out)
+        dev = grad_out.device
+        need_xyz, need_new, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and c > 0
+        gx = torch.empty(b, n, 3, device=dev, dtype=torch.float32) if need_xyz else None
+        gn = torch.empty(b, m, 3, device=dev, dtype=torch.float32) if need_new else None
+        gf = torch.empty(b, c, n, device=dev, dtype=torch.float32) if need_f else None
+        with torch.cuda.device(dev):
+            check(lib.sn_ball_group_backward(b, n, m, c, ns, u, ptr(idx), ptr(grad_out), ptr(gf), ptr(gx), ptr(gn), _stream(grad_out)),
+                  "sn_ball_group_backward")
+        return gx, gn, gf, None, None, None, None
+
+
+def ball_group(radius, nsample, xyz, new_xyz, features=None, use_xyz=True, rule="squared", return_idx=False):
+    """QueryAndGroup as one differentiable op: xyz (B,N,3), new_xyz (B,M,3), features (B,C,N) or None ->
+    (B, 3 use_xyz + C, M, nsample): with use_xyz the first three channels are xyz[idx] - new_xyz, then features[:, :, idx], idx the
+    ball query's rows (ops.ball_query).  Gradients reach features, xyz and new_xyz where each requires one (the indices are constants).
+    return_idx: also the indices (B,M,nsample) int32 and the counts (B,M) int32."""
+    if features is None and not use_xyz:
+        raise ValueError("ball_group: nothing to group (features is None and use_xyz is False)")
+    out, idx, cnt = BallGroupFunction.apply(xyz, new_xyz, features, radius, nsample, bool(use_xyz), _ball_rule(rule))
+    return (out, idx, cnt) if return_idx else out
+
+
 # --------------------------------------------------------------------------------------------- SoftProjection
 def _grad_temperature(gsig, temperature, min_sigma):
     """d loss / dT from the d loss / d sigma partials (one tiny kernel): sigma = max(T^2, min_sigma), with torch.max's
