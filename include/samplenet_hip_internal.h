@@ -779,6 +779,23 @@ int sn_ball_group_forward(int b, int n, int m, int c, float radius, int nsample,
 int sn_ball_group_backward(int b, int n, int m, int c, int nsample, int use_xyz, const int *idx, const float *grad_out,
                            float *grad_features, float *grad_xyz, float *grad_new_xyz, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The three nearest known points of every unknown point: the query of a PointNet++ feature-propagation (up-sampling) layer
+ * (csrc/feature_propagate.hip; restated in numpy float32 by tests/interp_ref.py).  Stands in for Pointnet2_PyTorch's three_nn.
+ * That module's source is NOT at hand: the tie order and the filling with m < 3 are AS RECALLED and UNPINNED (like
+ * SN_BALL_RULE_SQUARED above).
+ * unknown (b,n,3): the points that receive features; known (b,m,3): the points that carry them.  All fp32, every operation
+ * rounded once, nothing contracted.  For unknown j and known k:  dx = u.x - k.x, dy, dz likewise;
+ * d2 = ((dx*dx) + (dy*dy)) + (dz*dz).  The three neighbours are the three smallest by (d2, k): strict < in an ascending walk, ties
+ * to the lower index (sn_knn's rule).  A NaN (or +inf) d2 is never selected.  With fewer than three selectable points the missing
+ * slots hold index 0 and d2 = +inf (an inverse-distance weight of 0).  Indices always lie in [0, m).
+ * idx (b,n,3) int32, required; dist2 (b,n,3) the squared distances and dist (b,n,3) = sqrtf(dist2), correctly rounded, what
+ * three_nn returns; either may be NULL.  A lane owns an unknown point, the known cloud is staged in LDS in chunks of 1024 points.
+ * One launch, no workspace, no atomics, deterministic, capturable.  Checked on the host before any device work: a negative size,
+ * m == 0 with b * n > 0, a NULL required pointer -> SN_ERR_BAD_ARGUMENT; b == 0 or n == 0 is a no-op that succeeds; more than
+ * 2^31 - 1 workgroups -> SN_ERR_UNSUPPORTED.  n and m are unbounded. */
+int sn_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2, float *dist, int *idx, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

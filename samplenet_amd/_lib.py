@@ -184,6 +184,7 @@ PROTOTYPES = {
     "sn_ball_query": [_i, _i, _i, _f, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp],
     "sn_ball_group_forward": [_i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sn_ball_group_backward": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sn_three_nn": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"sn_last_error_string": ctypes.c_char_p, "sn_workspace_bytes": ctypes.c_longlong,
              "sn_pairscan_workspace_bytes": ctypes.c_longlong, "sn_linear_forward_maxpool_wide_scratch_bytes": ctypes.c_longlong,

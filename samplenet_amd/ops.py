@@ -616,6 +616,48 @@ def ball_group(radius, nsample, xyz, new_xyz, features=None, use_xyz=True, rule=
     return (out, idx, cnt) if return_idx else out
 
 
+# --------------------------------------------------------------------------------------------- feature propagation
+def _one_device(who, *ts):
+    devs = {t.device for t in ts if t is not None}
+    if len(devs) > 1:
+        raise ValueError("%s: all tensors must live on one device, got %s" % (who, sorted(str(d) for d in devs)))
+
+
+def _two_clouds(who, unknown, known):
+    _one_device(who, unknown, known)
+    if unknown.dim() != 3 or unknown.shape[2] != 3 or known.dim() != 3 or known.shape[2] != 3 or known.shape[0] != unknown.shape[0]:
+        raise ValueError("%s: unknown must be (B,n,3) and known (B,m,3), got %s and %s" % (who, tuple(unknown.shape), tuple(known.shape)))
+    if known.shape[1] == 0 and unknown.shape[0] * unknown.shape[1] > 0:
+        raise ValueError("%s: the known cloud is empty" % who)
+
+
+def three_nn(unknown, known):
+    """The three nearest `known` points of every `unknown` point (no gradient): unknown (B,n,3), known (B,m,3) ->
+    dist (B,n,3), the distances themselves (square roots, as Pointnet2_PyTorch's three_nn returns), and idx (B,n,3) int32,
+    ascending by (squared distance, index); with m < 3 the missing slots hold index 0 and an infinite distance (sn_three_nn)."""
+    _need_gpu(unknown, known)
+    unknown, known = _f32c(unknown.detach()), _f32c(known.detach())
+    _two_clouds("three_nn", unknown, known)
+    b, n, _ = unknown.shape
+    dist = torch.empty(b, n, 3, device=unknown.device, dtype=torch.float32)
+    idx = torch.empty(b, n, 3, device=unknown.device, dtype=torch.int32)
+    with torch.cuda.device(unknown.device):
+        check(lib.sn_three_nn(b, n, known.shape[1], ptr(unknown), ptr(known), None, ptr(dist), ptr(idx), _stream(unknown)), "sn_three_nn")
+    return dist, idx
+
+
+def three_interpolate(features, idx, weight):
+    """features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n): sum_t weight[:, :, t] * features[:, :, idx[:, :, t]], on
+    WeightedGatherFunction at k = 3 (gradients to features and weight)."""
+    _need_gpu(features, idx, weight)
+    if features.dim() != 3 or idx.dim() != 3 or idx.shape[2] != 3 or tuple(weight.shape) != tuple(idx.shape) or idx.shape[0] != features.shape[0]:
+        raise ValueError("three_interpolate: features must be (B,C,m), idx and weight (B,n,3)")
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("three_interpolate: idx must be int32 (or int64, converted), got %s" % idx.dtype)
+    _one_device("three_interpolate", features, idx, weight)
+    return WeightedGatherFunction.apply(features, idx, weight)
+
+
 # --------------------------------------------------------------------------------------------- SoftProjection
 def _grad_temperature(gsig, temperature, min_sigma):
     """d loss / dT from the d loss / d sigma partials (one tiny kernel): sigma = max(T^2, min_sigma), with torch.max's
