@@ -68,6 +68,144 @@ def test_python_prototypes_cover_the_header(libpath):
     from samplenet_amd import _lib
 
     assert set(_header_functions()) == set(_lib.PROTOTYPES), set(_header_functions()) ^ set(_lib.PROTOTYPES)
+    assert set(_lib.RESTYPES) == set(_lib.PROTOTYPES)
+
+
+# one character per type a binding can hold: what _lib.parse_header maps to on the Python side, what _SIGNATURES spells in C++
+_CODES = {ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_double: "d", ctypes.c_longlong: "q", ctypes.c_ulonglong: "Q",
+          ctypes.c_void_p: "p", ctypes.c_char_p: "s", None: "v"}
+_SIGNATURES = r"""
+#include "samplenet_hip.h"
+#include "samplenet_hip_internal.h"
+template <class T> struct code;
+template <> struct code<int> { static constexpr char c = 'i'; };
+template <> struct code<float> { static constexpr char c = 'f'; };
+template <> struct code<double> { static constexpr char c = 'd'; };
+template <> struct code<long long> { static constexpr char c = 'q'; };
+template <> struct code<unsigned long long> { static constexpr char c = 'Q'; };
+template <> struct code<void> { static constexpr char c = 'v'; };
+template <class T> struct code<T *> { static constexpr char c = 'p'; };
+template <> struct code<const char *> { static constexpr char c = 's'; };
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> { static constexpr char s[] = {code<R>::c, code<A>::c..., 0}; };
+constexpr bool same(const char *a, const char *b) { for (; *a && *a == *b; ++a, ++b) {} return *a == *b; }
+"""
+
+
+def _signature(_lib, name):
+    return _CODES[_lib.RESTYPES[name]] + "".join(_CODES[t] for t in _lib.PROTOTYPES[name])
+
+
+def _compile_signature_asserts(tmp_path, tag, signatures):
+    import subprocess
+
+    src = tmp_path / (tag + ".cpp")
+    src.write_text(_SIGNATURES + "".join('static_assert(same(sig<decltype(&%s)>::s, "%s"), "%s");\n' % (n, s, n)
+                                         for n, s in sorted(signatures.items())))
+    return subprocess.run(["/opt/rocm/bin/hipcc", "-x", "c++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)],
+                          capture_output=True, text=True, timeout=300)
+
+
+def test_the_compiler_reads_the_headers_as_the_bindings_do(tmp_path, libpath):
+    """Every derived binding against the compiler's own reading of the two headers: one static_assert per entry compares the
+    declared function type, spelled as one character for the return type and one per argument, with the same spelling of
+    _lib.PROTOTYPES / RESTYPES.  The guard: the same unit with ONE argument of a long entry changed from int to float must fail
+    to compile and name that entry -- so a pass is not an assert that compares nothing."""
+    from samplenet_amd import _lib
+
+    good = {name: _signature(_lib, name) for name in _lib.PROTOTYPES}
+    assert len(good) >= 153 and set("".join(good.values())) == set("ifdqQps")  # (no entry returns void today)
+    r = _compile_signature_asserts(tmp_path, "good", good)
+    assert r.returncode == 0, r.stderr[-3000:]
+    victim = "sn_fc_chain_forward_pool_out"
+    pos = next(p for p in range(30, len(good[victim]) - 1) if _lib.PROTOTYPES[victim][p] is ctypes.c_int)
+    flipped = good[victim][:1 + pos] + "f" + good[victim][2 + pos:]
+    assert len(flipped) == len(good[victim]) and sum(a != b for a, b in zip(flipped, good[victim])) == 1
+    r = _compile_signature_asserts(tmp_path, "flipped", dict(good, **{victim: flipped}))
+    assert r.returncode != 0 and r.stderr.count(" error: ") == 1 and victim in r.stderr, r.stderr[-3000:]
+
+
+_REFUSED = {
+    "a-scalar-type-outside-the-list-size_t": ("int sn_x(size_t count, sn_stream_t stream);", ("sn_x", "count", "size_t")),
+    "a-scalar-type-outside-the-list-unsigned": ("int sn_x(int n, unsigned flags);", ("sn_x", "flags", "unsigned")),
+    "a-scalar-type-outside-the-list-bool": ("int sn_x(bool on);", ("sn_x", "on", "bool")),
+    "a-return-type-outside-the-list": ("short sn_x(int n);", ("sn_x", "short")),
+    "an-unnamed-parameter": ("int sn_x(int n, const float *, sn_stream_t stream);", ("sn_x", "parameter 1", "no name")),
+    "an-unnamed-scalar": ("int sn_x(int, float *out);", ("sn_x", "parameter 0", "no name")),
+    "an-array-parameter": ("int sn_x(int n, float axis[3]);", ("sn_x", "parameter 1", "array")),
+    "a-function-pointer-parameter": ("int sn_x(int n, void (*done)(int, void *), void *arg);", ("sn_x", "done", "function pointer")),
+    "a-struct-by-value": ("typedef struct sn_r { int a; } sn_r;\nint sn_x(sn_r recipe, sn_stream_t stream);", ("sn_x", "recipe", "sn_r")),
+    "a-struct-by-value-spelled-struct": ("int sn_x(struct sn_r recipe);", ("sn_x", "recipe", "struct sn_r")),
+    "a-variadic-list": ("int sn_x(const char *fmt, ...);", ("sn_x", "parameter 1", "variadic")),
+    "half-a-declaration-no-closing-parenthesis": ("int sn_x(int n;\nint sn_y(int n);", ("sn_x",)),
+    "half-a-declaration-no-semicolon": ("int sn_y(int n);\nint sn_x(int n)\n", ("sn_x",)),
+    "half-a-declaration-an-attribute-behind-it": ("int sn_x(int n) __attribute__((cold));", ("sn_x",)),
+    "a-definition": ("int sn_x(int n) { return n; }", ("sn_x",)),
+    "a-variable": ("extern int sn_count;", ("sn_count",)),
+    "the-same-name-twice": ("int sn_x(int n);\nint sn_x(int n, int m);", ("sn_x", "twice")),
+}
+
+
+@pytest.mark.parametrize("cid", _REFUSED)
+def test_header_parser_refuses_what_it_cannot_map(libpath, cid):
+    """_lib.parse_header never guesses: a type with no ctypes counterpart in its table, a parameter without a name, an array, a
+    function pointer, a struct by value, a variadic list or text it can match only half of is an error that names the function
+    and the parameter."""
+    from samplenet_amd import _lib
+
+    text, named = _REFUSED[cid]
+    with pytest.raises(ValueError) as e:
+        _lib.parse_header(text)
+    assert all(word in str(e.value) for word in named), str(e.value)
+
+
+def test_header_parser_on_comments_and_every_accepted_type(libpath, monkeypatch):
+    from samplenet_amd import _lib
+
+    i, vp = ctypes.c_int, ctypes.c_void_p
+    args, res = _lib.parse_header("""
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define SN_X 1 /* int sn_in_a_define(int n); */
+        typedef void *sn_stream_t;
+        /* prose with a call, sn_conv_stack_backward(step_tail), and a whole prototype:
+         * int sn_in_a_block_comment(int n, float *out); */
+        // int sn_in_a_line_comment(int n);
+        const char *sn_text(void);
+        void sn_nothing( void );
+        unsigned long long sn_every(int n, const int m, float f, double d, long long q, unsigned long long Q, const char *name,
+                                    char *buf, const float *const *W, long long *const *t, const void *blob, unsigned *sync,
+                                    const sn_r *recipe, sn_stream_t stream);   // int sn_behind_code(int n);
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    assert list(args) == ["sn_text", "sn_nothing", "sn_every"]
+    assert args["sn_text"] == [] and res["sn_text"] is ctypes.c_char_p and args["sn_nothing"] == [] and res["sn_nothing"] is None
+    assert args["sn_every"] == [i, i, ctypes.c_float, ctypes.c_double, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_char_p,
+                                vp, vp, vp, vp, vp, vp, vp] and res["sn_every"] is ctypes.c_ulonglong
+    # a header that is not there: an ImportError that names it, like the missing library's
+    monkeypatch.setattr(_lib, "HEADERS", [_lib.HEADERS[0], os.path.join(ROOT, "include", "no_such_header.h")])
+    with pytest.raises(ImportError, match="no_such_header.h not found"):
+        _lib._parse_headers()
+
+
+def test_bindings_of_the_entries_that_are_not_only_int_and_pointer(libpath):
+    from samplenet_amd import _lib
+
+    i, f, d, vp, q = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_longlong
+    want = {"sn_adam_update": ([i, vp, vp, vp, vp, d, d, d, d, d, i, vp], i),
+            "sn_batch_assemble": ([i, i, i, i, i, vp, vp, vp, ctypes.c_ulonglong, i, i, q, vp, vp, i, vp, vp, vp, vp, vp, vp], i),
+            "sn_workspace_bytes": ([ctypes.c_char_p, i, i, i, i], q),
+            "sn_last_error_string": ([], ctypes.c_char_p),
+            "sn_bn_finalize": ([i, i, q, vp, vp, vp, f, f, vp, vp, vp, vp, vp], i),
+            "sn_ball_query": ([i, i, i, f, i, i, vp, i, vp, i, vp, vp, vp], i)}
+    for name, (argtypes, restype) in want.items():
+        assert _lib.PROTOTYPES[name] == argtypes and _lib.RESTYPES[name] is restype, name
+        assert list(getattr(_lib.lib, name).argtypes or []) == argtypes and getattr(_lib.lib, name).restype is restype, name
+    with pytest.raises(ImportError, match=r"does not export sn_no_such_entry \(stale build\?\)"):
+        _lib.bind(_lib.lib, ["sn_knn", "sn_no_such_entry"])
 
 
 def test_argument_errors_are_reported_without_a_gpu(libpath):

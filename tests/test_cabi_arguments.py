@@ -8,14 +8,11 @@ valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain a
 step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device), and the ten per-layer entries of the PointNet MLP (tests/test_gpu_mlp.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cabi_runner import check_case, run_cases
+
 BAD, UNSUP = 10001, 10002
 Pp = "PTR"    # a non-NULL (never dereferenced) device pointer
 HOSTI = "HOSTI"  # a real host int array {4}: sn_prefix_point_minima reads its prefix sizes on the host
@@ -486,37 +483,10 @@ CASES = _cases()
 IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + sorted(FC_CHAIN) + sorted(MLP) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
                                                "sn_skinny_linear_scratch_bytes"]
 
-_CHILD = r"""
-import ctypes, json, sys
-sys.path.insert(0, %r)
-from samplenet_amd._lib import lib
-cases = json.load(sys.stdin)
-host = (ctypes.c_int * 1)(4)
-hostp = (ctypes.c_void_p * 1)(4096)
-def host_array(a):  # ["HOSTI", ints...] / ["HOSTP", addresses...; 0 = NULL]
-    ty = ctypes.c_int if a[0] == "HOSTI" else ctypes.c_void_p
-    return (ty * (len(a) - 1))(*[(v or None) if a[0] == "HOSTP" else v for v in a[1:]])
-res = []
-for cid, name, args, _, _ in cases:
-    keep = [host_array(a) if isinstance(a, list) else a for a in args]
-    conv = [ctypes.c_void_p(4096) if a == "PTR" else (ctypes.cast(host, ctypes.c_void_p) if a == "HOSTI" else
-            (ctypes.cast(hostp, ctypes.c_void_p) if a == "HOSTP" else (ctypes.cast(a, ctypes.c_void_p) if isinstance(a, ctypes.Array) else a)))
-            for a in keep]
-    rc = getattr(lib, name)(*conv)
-    res.append([cid, int(rc), (lib.sn_last_error_string() or b"").decode()])
-print("RESULTS " + json.dumps(res))
-"""
-
 
 @pytest.fixture(scope="module")
 def results():
-    env = dict(os.environ)
-    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")  # argument checks need no device: none is offered
-    p = subprocess.run([sys.executable, "-c", _CHILD % ROOT], input=json.dumps(CASES), capture_output=True, text=True, env=env,
-                       timeout=600)
-    assert p.returncode == 0, p.stderr[-3000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULTS ")][-1]
-    return {cid: (rc, msg) for cid, rc, msg in json.loads(line[len("RESULTS "):])}
+    return run_cases(CASES)
 
 
 def test_the_table_walks_every_entry_in_scope():
@@ -552,12 +522,7 @@ def test_the_table_walks_every_entry_in_scope():
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_argument_table(results, case):
-    cid, name, args, want, text = case
-    rc, msg = results[cid]
-    assert rc == want, (cid, rc, msg)
-    if text is not None:
-        assert text in msg, (cid, msg)
-        assert msg.startswith(name + ":"), (cid, msg)  # the entry's own name, not that of a shared implementation
+    check_case(results, case)
 
 
 def test_size_queries():

@@ -1117,7 +1117,7 @@ def test_fp32_mfma_twin_agrees_with_the_split_bf16_build(tmp_path):
     import ctypes
     import subprocess
 
-    from samplenet_amd._lib import LIB_PATH, PROTOTYPES
+    from samplenet_amd._lib import LIB_PATH, bind
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     objs = [os.path.join(root, "samplenet_amd", "lib", n + ".o") for n in ("capi_common", "pairscan", "geometry_ops", "emd", "fc_chain", "task_network")]
@@ -1132,13 +1132,8 @@ def test_fp32_mfma_twin_agrees_with_the_split_bf16_build(tmp_path):
                                "-o", twins[-1], "-DSN_BF16X3=0"] + flags, timeout=900)
     so = str(tmp_path / "libsamplenet_hip_fp32.so")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", so] + twins + objs, timeout=600)
-    libs = []
-    for path in (LIB_PATH, so):
-        L = ctypes.CDLL(path)
-        for name in ("sn_linear_forward", "sn_conv_backward_partials", "sn_linear_wgrad_splits", "sn_linear_stats_blocks"):
-            getattr(L, name).argtypes = PROTOTYPES[name]
-            getattr(L, name).restype = ctypes.c_int
-        libs.append(L)
+    libs = [bind(ctypes.CDLL(path), ("sn_linear_forward", "sn_conv_backward_partials", "sn_linear_wgrad_splits", "sn_linear_stats_blocks"))
+            for path in (LIB_PATH, so)]
     g = torch.Generator(device="cuda").manual_seed(2)
     R, Ci, Co = 4096, 64, 128
     a = torch.randn(R, Ci, device="cuda", generator=g)

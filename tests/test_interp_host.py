@@ -3,18 +3,14 @@
 launch rule; and the host half of the entry's contract: argument errors and no-op cases in a child process that sees no GPU,
 RuntimeError on CPU tensors, the prototypes, PointnetFPModule's construction.  No GPU."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import interp_ref as R
+from cabi_runner import check_case, run_cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOOP_SHAPES = [s for s in R.SHAPES if s[0] * s[1] * s[2] <= 70000]  # the row loop is Python: every row but the three largest clouds (two queries of those)
 
 
@@ -167,27 +163,10 @@ def _cases():
 
 CASES = _cases()
 
-_CHILD = r"""
-import ctypes, json, sys
-sys.path.insert(0, %r)
-from samplenet_amd._lib import lib
-res = []
-for cid, name, args, _, _ in json.load(sys.stdin):
-    conv = [ctypes.c_void_p(4096) if a == "PTR" else a for a in args]
-    rc = getattr(lib, name)(*conv)
-    res.append([cid, int(rc), (lib.sn_last_error_string() or b"").decode()])
-print("RESULTS " + json.dumps(res))
-"""
-
 
 @pytest.fixture(scope="module")
 def results():
-    env = dict(os.environ)
-    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")  # argument checks need no device: none is offered
-    p = subprocess.run([sys.executable, "-c", _CHILD % ROOT], input=json.dumps(CASES), capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stderr[-3000:]
-    line = [l for l in p.stdout.splitlines() if l.startswith("RESULTS ")][-1]
-    return {cid: (rc, msg) for cid, rc, msg in json.loads(line[len("RESULTS "):])}
+    return run_cases(CASES)
 
 
 def test_the_tables_match_the_prototypes():
@@ -203,12 +182,7 @@ def test_the_tables_match_the_prototypes():
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_argument_table(results, case):
-    cid, name, args, want, text = case
-    rc, msg = results[cid]
-    assert rc == want, (cid, rc, msg)
-    if text is not None:
-        assert text in msg, (cid, msg)
-        assert msg.startswith(name + ":"), (cid, msg)  # the entry's own name
+    check_case(results, case)
 
 
 def test_cpu_tensors_raise():

@@ -160,15 +160,9 @@ def test_entries_in_header_prototypes_and_library():
     assert not any(name in open(os.path.join(ROOT, "include", "samplenet_hip.h")).read() for name in ENTRIES)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in ENTRIES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, code)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(",")]
-        proto = _lib.PROTOTYPES[name]
-        assert len(params) == len(proto), name
-        for p, t in zip(params, proto):  # ints by value, everything else a pointer / the stream handle
-            assert (t is ctypes.c_int) == (p.startswith("int ") and "*" not in p), (name, p)
-        assert hasattr(lib, name)
+    for name in ENTRIES:  # (their exact types: the compiler check of tests/test_cabi_and_host.py)
+        assert re.search(r"\bint\s+%s\s*\(" % name, code), name
+        assert name in _lib.PROTOTYPES and hasattr(lib, name), name
     assert "qdataset.py:62-95" in text and "main.py:540-555" in text
     # argument errors are reported before any device work; B = 0 is a no-op
     assert _lib.lib.sn_pose_error_forward(-1, None, None, None, None, None, None, None) == 10001
