@@ -796,6 +796,47 @@ int sn_ball_group_backward(int b, int n, int m, int c, int nsample, int use_xyz,
  * 2^31 - 1 workgroups -> SN_ERR_UNSUPPORTED.  n and m are unbounded. */
 int sn_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2, float *dist, int *idx, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * The gradient of a weighted gather towards its features by INVERTED INDEX (csrc/feature_propagate.hip; restated in numpy by
+ * tests/gather_inv_ref.py): the deterministic sum of sn_weighted_gather_backward_ordered (samplenet_hip.h) without its scratch
+ * buffer, for the regime of a feature-propagation layer (thousands of queries, hundreds of channels, a small destination cloud).
+ * A cloud has n destination rows and ne = m * k entries, entry e = j*k + t being neighbour t of query j; idx[b,e] names the
+ * entry's row.  An entry whose index lies outside [0, n) belongs to no row (as in sn_weighted_gather_backward_ordered).
+ *
+ * sn_gather_invert: idx (b,ne) int32 -> start (b,n+1) int32, order (b,ne) int32, both fully determined and fully overwritten:
+ *   start[b,r] = the number of valid entries of cloud b with idx < r (start[b,0] = 0, start[b,n] = the number of valid entries);
+ *   order[b, 0 .. start[b,n]) = the valid entry numbers sorted by (idx[e], e) -- a stable sort: row r's list is
+ *   order[b, start[b,r] .. start[b,r+1]) and ascends in e; every slot from start[b,n] on holds -1.
+ *   One launch, one workgroup of 16 waves per cloud: the counts by integer LDS atomics, 4096 rows at a time (n is not bounded by
+ *   LDS), a scan, then a placement that walks the entries in ascending order: a wave owns R consecutive rows, R the smallest power
+ *   of two <= 64 with 16 R >= n (so a cloud of up to 1024 rows is shared by all 16 waves in one pass), a lane one row and its
+ *   cursor; the wave reads all ne indices once per group of R rows it owns and places, one by one, those that name its rows.  No
+ *   workspace but the outputs, no memset, no synchronisation: deterministic, capturable.  idx must not change while the call runs.
+ *   BOUND: sn_gather_invert_supported(n, ne) = 1 iff ceil(n / 64) * ne <= 2^26 (and n < 2^31 - 1).  The product is the bound's
+ *   DEFINITION, not an exact read count (a wave reads ceil(ceil(n / R) / 16) * ne indices: ne up to n = 1024, about n / 1024 * ne
+ *   beyond); it is the bound up to which sn_weighted_gather_backward_ordered's own sum is ordered, so the inverted route exists
+ *   exactly where the two can be held bit for bit.  Beyond it the call returns SN_ERR_UNSUPPORTED and leaves the outputs untouched.
+ *   (n = 16385 admits ne up to 261 123.)
+ *   Checked on the host before any device work, in this order: a negative size -> SN_ERR_BAD_ARGUMENT; b == 0 or n == 0 is a
+ *   no-op that succeeds; start NULL, or idx / order NULL with ne > 0 -> SN_ERR_BAD_ARGUMENT; the bound.
+ *
+ * sn_weighted_gather_backward_inverted: weights (b,m,k), grad_out (b,c,m), start / order as above -> grad_X (b,c,n), OVERWRITTEN:
+ *   grad_X[b,ch,r] = the fp32 sum over i in [start[b,r], start[b,r+1]), in that order and starting from +0, of
+ *   fl(grad_out[b,ch,e/k] * weights[b,e]) with e = order[b,i]: the product rounded, then added, nothing contracted.  A row with no
+ *   entry receives +0.  This is the arithmetic of sn_weighted_gather_backward_ordered: with start / order from sn_gather_invert on
+ *   the same idx the two grad_X are BIT-IDENTICAL.  idx itself is not an argument: the lists carry all it says.  The gradient towards
+ *   the weights stays with sn_weighted_gather_backward (grad_X = NULL).
+ *   One launch: a thread owns one row and 8 channels of it (entry number, query and weight loaded once per entry for the 8
+ *   accumulators); lists are not split, so a launch takes as long as its longest list.  No atomics, no scratch, capturable.
+ *   A start outside [0, m*k] is clamped and an entry number outside [0, m*k) skipped: foreign buffers cannot make it read elsewhere.
+ *   Checked on the host: a negative size, k < 1, m * k beyond 2^31 - 1 -> SN_ERR_BAD_ARGUMENT; b == 0, c == 0 or n == 0 is a no-op
+ *   that succeeds; start or grad_X NULL, or weights / grad_out / order NULL with m > 0 -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1
+ *   workgroups (b * ceil(n * ceil(c / 8) / 256)) -> SN_ERR_UNSUPPORTED. */
+int sn_gather_invert_supported(int n, int ne);
+int sn_gather_invert(int b, int n, int ne, const int *idx, int *start, int *order, sn_stream_t stream);
+int sn_weighted_gather_backward_inverted(int b, int c, int n, int m, int k, const float *weights, const float *grad_out,
+                                         const int *start, const int *order, float *grad_X, sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

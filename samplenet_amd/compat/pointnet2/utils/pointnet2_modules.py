@@ -4,7 +4,8 @@
         -> (B, mlp[-1], n)
 
 forward reads as the original's: three_nn (sn_three_nn), the inverse-distance weights 1 / (dist + 1e-8) normalised over the three
-neighbours as torch operations, three_interpolate (WeightedGatherFunction at k = 3) and torch.cat with the skip features; the
+neighbours as torch operations, three_interpolate (sn_weighted_gather_forward at k = 3; the features' gradient by inverted index,
+ops.ThreeInterpolateFunction) and torch.cat with the skip features; the
 shared MLP behind them is plain torch: per layer a 1 x 1 Conv2d (with a bias only without BatchNorm), BatchNorm2d, ReLU, applied on
 unsqueeze(-1).  The original's sources are not at hand: the state_dict key names of `self.mlp` ("<i>.conv.weight",
 "<i>.bn.weight", ..), the weight expression and the tie order of the query (pointnet2_utils) are AS RECALLED and UNPINNED.

@@ -141,6 +141,162 @@ int fp_grid(const char *who, int b, int n, int *groups, int *waves, unsigned *gr
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The interpolation's gradient towards the features by INVERTED INDEX.  grad_X[b,ch,r] is the sum, in ascending entry order, of
+// grad_out[b,ch,e/k] * weights[b,e] over the entries e = j*k + t whose index names row r.  The list of those entries depends on idx
+// alone: gather_invert_kernel builds it once per cloud (start: where each row's list begins; order: the entry numbers, row by row,
+// each list ascending), gather_bwd_inverted_kernel walks it for every channel and forms the product where it is consumed -- no
+// contribution is stored, nothing is added atomically, and the sequence of fp32 operations per element is that of
+// weighted_gather_bwd_kernel + index_add_ordered_kernel (geometry_ops.hip): bit-identical to sn_weighted_gather_backward_ordered.
+constexpr int kInvThreads = 1024;     // one workgroup per cloud
+constexpr int kInvWaves = kInvThreads / kWave;
+constexpr int kInvTile = 4096;        // destination rows counted in LDS at a time (16 KB); n is not bounded by it
+constexpr int kInvPer = kInvTile / kInvThreads;
+constexpr int kInvBatch = 4;          // trips of 64 entries whose indices the placement loads at once
+// the support bound: ceil(n / 64) * ne, the index loads of index_add_ordered_kernel, held to its kIndexAddOrderedWork
+// (geometry_ops.hip), so the inverted route exists exactly where the ordered route's sum is ordered (the placement below reads
+// fewer: ne per wave up to n = 1024, about n / 1024 * ne beyond)
+constexpr long long kInvWork = 1ll << 26;
+
+bool invert_supported(long long n, long long ne) { return n >= 0 && ne >= 0 && n < INT_MAX && ne <= INT_MAX && ((n + 63) / 64) * ne <= kInvWork; }
+
+// grid = b, block = kInvThreads.  Phase A, tile by tile of kInvTile rows: the valid entries of each row counted with integer LDS
+// atomics (an integer sum has no order), an exclusive scan over the tile carried on from the tiles before it -> start.  Phase B:
+// a wave owns up to 64 rows (a lane one row and its cursor) and walks the cloud's entries in ascending order, 64 per trip, visiting
+// only those that name one of its rows -- index_add_ordered_kernel's ballot walk without the channel loop -- so every list ascends.
+__global__ void __launch_bounds__(kInvThreads) gather_invert_kernel(int n, int ne, const int *__restrict__ idx, int *start, int *__restrict__ order)
+{
+    __shared__ int cnt[kInvTile];
+    __shared__ int wave_sum[kInvWaves];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    idx += (size_t)blockIdx.x * ne;
+    order += (size_t)blockIdx.x * ne;
+    start += (size_t)blockIdx.x * ((size_t)n + 1);
+
+    int base = 0;  // valid entries below this tile's first row (the same in every thread)
+    for (long long r0 = 0; r0 < n; r0 += kInvTile) {
+        const int tn = n - r0 < kInvTile ? (int)(n - r0) : kInvTile;
+        for (int i = tid; i < kInvTile; i += kInvThreads) cnt[i] = 0;
+        __syncthreads();
+        for (int e = tid; e < ne; e += kInvThreads) {
+            const long long r = (long long)idx[e] - r0;
+            if (r >= 0 && r < tn) atomicAdd(&cnt[(int)r], 1);
+        }
+        __syncthreads();
+        int c[kInvPer], mine = 0;  // thread t owns rows t * kInvPer .. of the tile (counts past tn are zero)
+#pragma unroll
+        for (int q = 0; q < kInvPer; ++q) c[q] = cnt[tid * kInvPer + q], mine += c[q];
+        int incl = mine;  // inclusive scan over the wave's lanes
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int up = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += up;
+        }
+        if (lane == kWave - 1) wave_sum[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kInvWaves; ++w) {
+            const int s = wave_sum[w];
+            before += w < wave ? s : 0;
+            total += s;
+        }
+        int at = base + before + incl - mine;
+#pragma unroll
+        for (int q = 0; q < kInvPer; ++q) {
+            if (tid * kInvPer + q < tn) start[r0 + tid * kInvPer + q] = at;
+            at += c[q];
+        }
+        base += total;
+        __syncthreads();  // cnt and wave_sum are free again; this tile's start[] is visible to the workgroup
+    }
+    if (tid == 0) start[n] = base;
+    for (int i = base + tid; i < ne; i += kInvThreads) order[i] = -1;  // the slots no valid entry fills
+
+    // rows per wave: the smallest power of two R <= 64 with 16 R >= n, so that a small cloud's walk is shared by all the waves
+    int R = 1;
+    while (R < kWave && R * kInvWaves < n) R <<= 1;
+    const int groups = (int)(((long long)n + R - 1) / R);
+    for (int g = wave; g < groups; g += kInvWaves) {
+        const long long row0 = (long long)g * R, row = row0 + lane;
+        int cur = lane < R && row < n ? start[row] : 0;
+        // kInvBatch trips' indices are loaded before any of their stores: the wait for a trip's load also waits for the stores
+        // issued before it (one counter), so the loads go first, once per batch
+        for (int e0 = 0; e0 < ne; e0 += kInvBatch * kWave) {
+            int id[kInvBatch];
+#pragma unroll
+            for (int u = 0; u < kInvBatch; ++u) id[u] = e0 + u * kWave + lane < ne ? idx[e0 + u * kWave + lane] : -1;
+#pragma unroll
+            for (int u = 0; u < kInvBatch; ++u) {
+                const long long off = (long long)id[u] - row0;
+                sn_u64 hits = __ballot(off >= 0 && off < R && id[u] < n);
+                while (hits) {
+                    const int t = __builtin_ctzll(hits);
+                    hits &= hits - 1;
+                    if ((long long)__builtin_amdgcn_readlane(id[u], t) == row) order[cur++] = e0 + u * kWave + t;
+                }
+            }
+        }
+    }
+}
+
+constexpr int kGbThreads = 256;
+constexpr int kGbChannels = 8;  // channels a thread accumulates in registers: entry number, query and weight are loaded once for all
+constexpr int kGbBatch = 4;     // entries of a list whose operands are in flight together
+
+// A thread owns one destination row and kGbChannels channels of it.  Threads are numbered row-fastest over (channel block, row) of
+// a cloud, so a wave's stores run along r (coalesced) and at n < 64 a wave still has 64 busy lanes.  The reads of grad_out are
+// scattered over one cloud's channel planes (m floats each): cache hits.
+__global__ void __launch_bounds__(kGbThreads) gather_bwd_inverted_kernel(int c, int n, int m, int k, int blocks, const float *__restrict__ w,
+                                                                        const float *__restrict__ go, const int *__restrict__ start,
+                                                                        const int *__restrict__ order, float *__restrict__ gX)
+{
+    const int cloud = blockIdx.x / blocks;
+    const long long t = (long long)(blockIdx.x - cloud * blocks) * kGbThreads + threadIdx.x;
+    const long long cb = t / n;
+    const int row = (int)(t - cb * n);
+    const long long ch0 = cb * kGbChannels;
+    if (ch0 >= c) return;
+    const int nch = c - ch0 < kGbChannels ? (int)(c - ch0) : kGbChannels;
+    const int ne = m * k;
+    w += (size_t)cloud * ne;
+    order += (size_t)cloud * ne;
+    start += (size_t)cloud * ((size_t)n + 1);
+    go += ((size_t)cloud * c + ch0) * m;
+    gX += ((size_t)cloud * c + ch0) * n + row;
+    float acc[kGbChannels];
+#pragma unroll
+    for (int q = 0; q < kGbChannels; ++q) acc[q] = 0.f;
+    // (a start outside [0, ne] or an entry number outside [0, ne) can only come from a caller's own buffers: nothing is read there)
+    const int lo = max(start[row], 0), hi = min(start[row + 1], ne);
+    // kGbBatch entries at a time: their entry numbers, then their weights and gradients, are loaded side by side (two memory
+    // latencies per batch instead of per entry); the sums still take the entries one by one, in list order
+    for (int i = lo; i < hi; i += kGbBatch) {
+        int e[kGbBatch];
+        float wt[kGbBatch], gv[kGbBatch][kGbChannels];
+#pragma unroll
+        for (int u = 0; u < kGbBatch; ++u) e[u] = i + u < hi ? order[i + u] : -1;
+#pragma unroll
+        for (int u = 0; u < kGbBatch; ++u) {
+            const int at = (unsigned)e[u] < (unsigned)ne ? e[u] : 0;  // (an entry that is skipped below reads entry 0's operands)
+            wt[u] = w[at];
+            const float *g = go + (unsigned)at / (unsigned)k;
+#pragma unroll
+            for (int q = 0; q < kGbChannels; ++q) gv[u][q] = q < nch ? g[(size_t)q * m] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < kGbBatch; ++u) {
+            if ((unsigned)e[u] >= (unsigned)ne) continue;
+#pragma unroll
+            for (int q = 0; q < kGbChannels; ++q)
+                if (q < nch) acc[q] += gv[u][q] * wt[u];  // product rounded, then added: weighted_gather_bwd_kernel's g * wt
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kGbChannels; ++q)
+        if (q < nch) gX[(size_t)q * n] = acc[q];
+}
+
 }  // namespace
 }  // namespace sn
 
@@ -159,6 +315,36 @@ extern "C" int sn_three_nn(int b, int n, int m, const float *unknown, const floa
     if (int rc = fp_grid(__func__, b, n, &a.groups, &waves, &grid)) return rc;
     a.n = n, a.m = m, a.unknown = unknown, a.known = known, a.idx = idx, a.dist2 = dist2, a.dist = dist;
     hipLaunchKernelGGL(three_nn_kernel, dim3(grid), dim3(waves * kWave), 0, (hipStream_t)stream, a);
+    SN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sn_gather_invert_supported(int n, int ne) { return invert_supported(n, ne) ? 1 : 0; }
+
+extern "C" int sn_gather_invert(int b, int n, int ne, const int *idx, int *start, int *order, sn_stream_t stream)
+{
+    SN_REQUIRE(b >= 0 && n >= 0 && ne >= 0, "negative size");
+    if (b == 0 || n == 0) return 0;
+    SN_REQUIRE(start && (ne == 0 || (idx && order)), "null pointer");
+    if (!invert_supported(n, ne))
+        return sn_set_error(SN_ERR_UNSUPPORTED, "%s: ceil(n / 64) * ne = %lld exceeds 2^26 (sn_gather_invert_supported)", __func__,
+                            ((long long)n + 63) / 64 * ne);
+    hipLaunchKernelGGL(gather_invert_kernel, dim3(b), dim3(kInvThreads), 0, (hipStream_t)stream, n, ne, idx, start, order);
+    SN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sn_weighted_gather_backward_inverted(int b, int c, int n, int m, int k, const float *weights, const float *grad_out,
+                                                    const int *start, const int *order, float *grad_X, sn_stream_t stream)
+{
+    SN_REQUIRE(b >= 0 && c >= 0 && n >= 0 && m >= 0 && k >= 1, "bad size");
+    SN_REQUIRE((long long)m * k <= INT_MAX, "m * k must fit in 31 bits");
+    if (b == 0 || c == 0 || n == 0) return 0;
+    SN_REQUIRE(start && grad_X && (m == 0 || (weights && grad_out && order)), "null pointer");
+    const long long blocks = ((long long)n * (((long long)c + kGbChannels - 1) / kGbChannels) + kGbThreads - 1) / kGbThreads;
+    if (blocks * b > INT_MAX) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
+    hipLaunchKernelGGL(gather_bwd_inverted_kernel, dim3((unsigned)(blocks * b)), dim3(kGbThreads), 0, (hipStream_t)stream, c, n, m, k,
+                       (int)blocks, weights, grad_out, start, order, grad_X);
     SN_LAUNCH_CHECK();
     return 0;
 }

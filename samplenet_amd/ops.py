@@ -646,16 +646,108 @@ def three_nn(unknown, known):
     return dist, idx
 
 
-def three_interpolate(features, idx, weight):
-    """features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n): sum_t weight[:, :, t] * features[:, :, idx[:, :, t]], on
-    WeightedGatherFunction at k = 3 (gradients to features and weight)."""
+class GatherInverse(NamedTuple):
+    """The inverted index of a gather (sn_gather_invert): row r of cloud b is named by the entries order[b, start[b,r] : start[b,r+1]],
+    ascending; order is -1 from start[b,-1] on."""
+    start: torch.Tensor  # (B, n+1) int32
+    order: torch.Tensor  # (B, ne) int32
+
+
+def gather_invert_supported(n, ne):
+    """Whether sn_gather_invert serves n destination rows and ne entries per cloud (ceil(n / 64) * ne <= 2^26)."""
+    return 0 <= n < 2 ** 31 and 0 <= ne < 2 ** 31 and bool(lib.sn_gather_invert_supported(n, ne))
+
+
+def gather_invert(idx, n):
+    """idx (B,m,k) or (B,ne), int32 (or int64, converted), naming rows of an n-row destination -> GatherInverse(start, order): per
+    destination row the entries e = j*k + t that name it, in ascending order (an index outside [0,n) belongs to no row).  It depends
+    on idx alone: build it once for an idx that serves several three_interpolate calls and pass it as their inverse=."""
+    _need_gpu(idx)
+    if idx.dim() not in (2, 3) or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("gather_invert: idx must be (B,m,k) or (B,ne), int32 or int64, got %s %s" % (tuple(idx.shape), idx.dtype))
+    idx = idx.detach().contiguous().int()
+    b, ne, n = idx.shape[0], idx.shape[1] * (idx.shape[2] if idx.dim() == 3 else 1), int(n)
+    if not gather_invert_supported(n, ne):
+        raise ValueError("gather_invert: n = %d rows with %d entries per cloud is beyond sn_gather_invert_supported" % (n, ne))
+    if n == 0:  # no row: no entry is valid (the entry itself is a no-op here)
+        return GatherInverse(torch.zeros(b, 1, device=idx.device, dtype=torch.int32), torch.full((b, ne), -1, device=idx.device, dtype=torch.int32))
+    start = torch.empty(b, n + 1, device=idx.device, dtype=torch.int32)
+    order = torch.empty(b, ne, device=idx.device, dtype=torch.int32)
+    with torch.cuda.device(idx.device):
+        check(lib.sn_gather_invert(b, n, ne, ptr(idx), ptr(start), ptr(order), _stream(idx)), "sn_gather_invert")
+    return GatherInverse(start, order)
+
+
+class ThreeInterpolateFunction(torch.autograd.Function):
+    """WeightedGatherFunction's forward; the gradient towards the features by inverted index (sn_gather_invert +
+    sn_weighted_gather_backward_inverted: the bits of the ordered route, without its (B,C,M,K) scratch buffer).  start / order: a
+    GatherInverse of idx the caller built, or None (built in backward).  Beyond sn_gather_invert_supported: the ordered route."""
+
+    @staticmethod
+    def forward(ctx, X, idx, w, start, order):
+        X, idx, w = _f32c(X), idx.contiguous().int(), _f32c(w)
+        B, C, N = X.shape
+        _, M, K = idx.shape
+        out = torch.empty(B, C, M, device=X.device, dtype=torch.float32)
+        with torch.cuda.device(X.device):
+            check(lib.sn_weighted_gather_forward(B, C, N, M, K, ptr(X), ptr(idx), ptr(w), ptr(out), _stream(X)),
+                  "sn_weighted_gather_forward")
+        ctx.save_for_backward(X, idx, w, start, order)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        X, idx, w, start, order = ctx.saved_tensors
+        B, C, N = X.shape
+        _, M, K = idx.shape
+        grad_out = grad_out.contiguous()
+        need_X, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        gX = torch.empty_like(X) if need_X else None
+        gw = torch.empty_like(w) if need_w else None
+        with torch.cuda.device(X.device):
+            if need_X and start is None and not gather_invert_supported(N, M * K):
+                scratch = torch.empty(B * C * M * K, device=X.device, dtype=torch.float32)
+                check(lib.sn_weighted_gather_backward_ordered(B, C, N, M, K, ptr(X), ptr(idx), ptr(w), ptr(grad_out), ptr(gw),
+                                                              ptr(gX), ptr(scratch), _stream(X)), "sn_weighted_gather_backward_ordered")
+                return gX, None, gw, None, None
+            if need_X:
+                if start is None:
+                    start = torch.empty(B, N + 1, device=X.device, dtype=torch.int32)
+                    order = torch.empty(B, M * K, device=X.device, dtype=torch.int32)
+                    check(lib.sn_gather_invert(B, N, M * K, ptr(idx), ptr(start), ptr(order), _stream(X)), "sn_gather_invert")
+                check(lib.sn_weighted_gather_backward_inverted(B, C, N, M, K, ptr(w), ptr(grad_out), ptr(start), ptr(order), ptr(gX),
+                                                               _stream(X)), "sn_weighted_gather_backward_inverted")
+            if need_w:
+                check(lib.sn_weighted_gather_backward(B, C, N, M, K, ptr(X), ptr(idx), ptr(w), ptr(grad_out), ptr(gw), None,
+                                                      _stream(X)), "sn_weighted_gather_backward")
+        return gX, None, gw, None, None
+
+
+def three_interpolate(features, idx, weight, inverse=None):
+    """features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n): sum_t weight[:, :, t] * features[:, :, idx[:, :, t]]
+    (gradients to features and weight).  The gradient towards the features is the deterministic ordered sum, taken by inverted
+    index; inverse: what ops.gather_invert(idx, m) returned for THIS idx (nothing else: a pair built by hand is checked for shape and
+    type only, and the gradient then follows whatever lists it holds), for a caller that reuses one idx; without it every backward
+    builds the inversion anew.  Beyond ops.gather_invert_supported(m, 3 n) the gradient takes the ordered route and no inverse exists."""
     _need_gpu(features, idx, weight)
     if features.dim() != 3 or idx.dim() != 3 or idx.shape[2] != 3 or tuple(weight.shape) != tuple(idx.shape) or idx.shape[0] != features.shape[0]:
         raise ValueError("three_interpolate: features must be (B,C,m), idx and weight (B,n,3)")
     if idx.dtype not in (torch.int32, torch.int64):
         raise ValueError("three_interpolate: idx must be int32 (or int64, converted), got %s" % idx.dtype)
     _one_device("three_interpolate", features, idx, weight)
-    return WeightedGatherFunction.apply(features, idx, weight)
+    if inverse is None:
+        return ThreeInterpolateFunction.apply(features, idx, weight, None, None)
+    start, order = inverse
+    b, m = features.shape[0], features.shape[2]
+    if not gather_invert_supported(m, idx.shape[1] * 3):
+        raise ValueError("three_interpolate: m = %d with %d entries per cloud is beyond sn_gather_invert_supported: no inverse exists "
+                         "for it (leave inverse=None for the ordered route)" % (m, idx.shape[1] * 3))
+    for t, shape, name in ((start, (b, m + 1), "start"), (order, (b, idx.shape[1] * 3), "order")):
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("three_interpolate: inverse.%s must be contiguous int32 %s (ops.gather_invert(idx, %d)), got %s %s"
+                             % (name, shape, m, tuple(t.shape), t.dtype))
+    _one_device("three_interpolate", features, start, order)
+    return ThreeInterpolateFunction.apply(features, idx, weight, start, order)
 
 
 # --------------------------------------------------------------------------------------------- SoftProjection
