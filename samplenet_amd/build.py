@@ -22,7 +22,18 @@ ARCH = "gfx950"
 SOURCES = [
     ("capi_common.cpp", []),
     ("pairscan.hip", ["-ffp-contract=off"]),
-    ("geometry_ops.hip", ["-ffp-contract=off"]),
+    # the Chamfer backward and the losses on it add the owners' terms in the reference's order (chamfer_owner.h: owner_sum)
+    ("chamfer_backward.hip", ["-ffp-contract=off"]),
+    # SoftProjection's backward (soft_query.h) and the gather / group ops with their ordered index-add
+    ("soft_projection.hip", ["-ffp-contract=off"]),
+    # the sampler step's fused loss: Chamfer and soft-projection backward of a query in one launch, the step tail, the surface values
+    ("sampler_step_loss.hip", ["-ffp-contract=off"]),
+    # PCRNet's output head and the quaternion rotation, apart and fused
+    ("pcrnet_head.hip", ["-ffp-contract=off"]),
+    # inference matching: numpy's fp64 distance, product then sum
+    ("nn_matching.hip", ["-ffp-contract=off"]),
+    # the progressive sampler's prefix minima, pack / pad ops and fused loss: the Chamfer scan's expression and tie rule
+    ("progressive_prefix.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),
     # the ranking's fp64 distance is numpy's: product then sum, one rounding per operation (tests/rank_ref.py)
     ("rank_points.hip", ["-ffp-contract=off"]),

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void batch_assemble_kernel(BatchArgs a)
 #pragma unroll
         for (int c = 0; c < 3; ++c) a.p0[base + sn::pt_off(a.layout, N, j, c)] = v[c];
         if (a.p1) {
-            // sn_qrot_forward's expression (geometry_ops.hip: qrot_fwd_kernel)
+            // sn_qrot_forward's expression (pcrnet_head.hip: qrot_fwd_kernel)
             const float uvx = qy * v[2] - qz * v[1], uvy = qz * v[0] - qx * v[2], uvz = qx * v[1] - qy * v[0];
             const float wx = qy * uvz - qz * uvy, wy = qz * uvx - qx * uvz, wz = qx * uvy - qy * uvx;
             float o[3] = {v[0] + 2.0f * (qw * uvx + wx), v[1] + 2.0f * (qw * uvy + wy), v[2] + 2.0f * (qw * uvz + wz)};

@@ -147,14 +147,14 @@ int fp_grid(const char *who, int b, int n, int *groups, int *waves, unsigned *gr
 // alone: gather_invert_kernel builds it once per cloud (start: where each row's list begins; order: the entry numbers, row by row,
 // each list ascending), gather_bwd_inverted_kernel walks it for every channel and forms the product where it is consumed -- no
 // contribution is stored, nothing is added atomically, and the sequence of fp32 operations per element is that of
-// weighted_gather_bwd_kernel + index_add_ordered_kernel (geometry_ops.hip): bit-identical to sn_weighted_gather_backward_ordered.
+// weighted_gather_bwd_kernel + index_add_ordered_kernel (soft_projection.hip): bit-identical to sn_weighted_gather_backward_ordered.
 constexpr int kInvThreads = 1024;     // one workgroup per cloud
 constexpr int kInvWaves = kInvThreads / kWave;
 constexpr int kInvTile = 4096;        // destination rows counted in LDS at a time (16 KB); n is not bounded by it
 constexpr int kInvPer = kInvTile / kInvThreads;
 constexpr int kInvBatch = 4;          // trips of 64 entries whose indices the placement loads at once
 // the support bound: ceil(n / 64) * ne, the index loads of index_add_ordered_kernel, held to its kIndexAddOrderedWork
-// (geometry_ops.hip), so the inverted route exists exactly where the ordered route's sum is ordered (the placement below reads
+// (soft_projection.hip), so the inverted route exists exactly where the ordered route's sum is ordered (the placement below reads
 // fewer: ne per wave up to n = 1024, about n / 1024 * ne beyond)
 constexpr long long kInvWork = 1ll << 26;
 

@@ -77,7 +77,7 @@ namespace sn {
 
 constexpr int kWave = 64;
 // spacing (in 32-bit words) of the words of an FC chain launch's `sync` state: word i lives at sync[i * kFcSyncStride], 128 bytes
-// apart (fc_chain.hip; geometry_ops.hip: the step tail reads the error words; samplenet_amd/pointnet.py mirrors it as SYNC_STRIDE)
+// apart (fc_chain.hip; sampler_step_loss.hip: the step tail reads the error words; samplenet_amd/pointnet.py mirrors it as SYNC_STRIDE)
 constexpr int kFcSyncStride = 32;
 constexpr sn_u64 kKeyInf = ~0ull;
 

@@ -2,7 +2,7 @@
 `registration/main.py --sampler fps|random` (main.py:279-287).
 
 Same constructor, `.name`, shape checks and torch RNG calls (order and devices) as the reference classes, so a seeded run
-picks the same points.  Underneath: ops.furthest_point_sample (sampling.hip) and the gather kernels of geometry_ops.hip.
+picks the same points.  Underneath: ops.furthest_point_sample (sampling.hip) and the gather kernels of soft_projection.hip.
 Two deliberate differences:
   * FPS reads a `bnc` cloud in place through the kernel's layout argument, and a `bnc` cloud is gathered without a
     transposed copy (ops.group_point);

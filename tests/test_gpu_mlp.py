@@ -1118,15 +1118,18 @@ def test_fp32_mfma_twin_agrees_with_the_split_bf16_build(tmp_path):
     import subprocess
 
     from samplenet_amd._lib import LIB_PATH, bind
+    from samplenet_amd.build import SOURCES
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    objs = [os.path.join(root, "samplenet_amd", "lib", n + ".o") for n in ("capi_common", "pairscan", "geometry_ops", "emd", "fc_chain", "task_network")]
+    remade = ("pointnet_mlp", "pointnet_mlp_backward")
+    # every other unit of the product build, by the build's own list
+    objs = [os.path.join(root, "samplenet_amd", "lib", n + ".o") for n in (os.path.splitext(src)[0] for src, _ in SOURCES) if n not in remade]
     if not all(os.path.exists(o) for o in objs):
         pytest.skip("object files of the product build are not in the tree")
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(root, "include"),
              "-I" + os.path.join(root, "samplenet_amd", "csrc"), "-Wno-unused-function"]
     twins = []
-    for unit in ("pointnet_mlp", "pointnet_mlp_backward"):
+    for unit in remade:
         twins.append(str(tmp_path / (unit + "0.o")))
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "-c", os.path.join(root, "samplenet_amd", "csrc", unit + ".hip"),
                                "-o", twins[-1], "-DSN_BF16X3=0"] + flags, timeout=900)

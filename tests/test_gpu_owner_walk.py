@@ -1,4 +1,4 @@
-"""The ordered owner sum of the Chamfer backward kernels (csrc/geometry_ops.hip: owner_sum), called through the raw C ABI in guarded
+"""The ordered owner sum of the Chamfer backward kernels (csrc/chamfer_owner.h: owner_sum), called through the raw C ABI in guarded
 buffers (tests/cabi_ref.py).  A query's gradient is its own term followed by one subtraction per cloud point it owns, in ascending
 point index; the kernels run that sum as a chain over the lanes of a wave, 16 list entries per chunk, from a list of CAP entries
 per wave; a query that owns more passes the slots once more per CAP owners.  The clouds are clusters around the queries, built so

@@ -14,5 +14,8 @@ printf '#include "pointnet_mlp.hip"\n#include "pointnet_mlp_backward.hip"\n#incl
 /opt/rocm/bin/hipcc -x hip -c tools/_ab/pointnet_mlp_tl.hip -o tools/_ab/pointnet_mlp_tl.o $F -DSN_TIMELINE $X
 /opt/rocm/bin/hipcc -x hip -c samplenet_amd/csrc/capi_common.cpp -o tools/_ab/capi_common_tl.o $F -DSN_TIMELINE
 /opt/rocm/bin/hipcc -x hip -c samplenet_amd/csrc/pairscan.hip -o tools/_ab/pairscan_tl.o $G
-/opt/rocm/bin/hipcc -x hip -c samplenet_amd/csrc/geometry_ops.hip -o tools/_ab/geometry_ops_tl.o $G
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o tools/_ab/libsamplenet_hip_tl.so tools/_ab/pointnet_mlp_tl.o tools/_ab/capi_common_tl.o tools/_ab/pairscan_tl.o tools/_ab/geometry_ops_tl.o samplenet_amd/lib/emd.o
+/opt/rocm/bin/hipcc -x hip -c samplenet_amd/csrc/sampler_step_loss.hip -o tools/_ab/sampler_step_loss_tl.o $G
+# the other geometric units carry no stamps: the product build's objects
+GEO=""
+for s in chamfer_backward soft_projection pcrnet_head nn_matching progressive_prefix; do GEO="$GEO samplenet_amd/lib/$s.o"; done
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o tools/_ab/libsamplenet_hip_tl.so tools/_ab/pointnet_mlp_tl.o tools/_ab/capi_common_tl.o tools/_ab/pairscan_tl.o tools/_ab/sampler_step_loss_tl.o $GEO samplenet_amd/lib/emd.o

@@ -9,7 +9,7 @@ mkdir -p tools/_ab
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Isamplenet_amd/csrc -Wall -Wno-unused-function"
 NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
 OBJS=""
-for s in capi_common pairscan geometry_ops sampling emd pointnet_mlp pointnet_mlp_backward fc_chain task_network cloud_transform optimizer batch_assemble; do
+for s in capi_common pairscan chamfer_backward soft_projection sampler_step_loss pcrnet_head nn_matching progressive_prefix sampling emd pointnet_mlp pointnet_mlp_backward fc_chain task_network cloud_transform optimizer batch_assemble; do
   hit=0
   for one in ${SRC//,/ }; do
     if [ "$s" == "${one%.*}" ]; then hit=1; fi
