@@ -332,7 +332,8 @@ int sn_linear_forward_maxpool(int R, int Ci, int Co, int npts, const float *ain,
  *                               of its 128 rows in registers for all of its columns, the weights are split once per call into
  *                               wplanes (3 * Co * Ci bf16; planes_ready != 0: already holds the split of this W); the maxima
  *                               leave as one key per column and min(128, npts) rows (scratch: _scratch_bytes) -- no atomics, no
- *                               clear; results bit-identical to sn_linear_forward_maxpool.  Query _supported. */
+ *                               clear; results bit-identical to sn_linear_forward_maxpool.  coef_prev == NULL (which the tile
+ *                               entry refuses): the operand is used as is, no ReLU.  Query _supported. */
 int sn_linear_forward_maxpool_wide_supported(int R, int Ci, int Co, int npts);
 long long sn_linear_forward_maxpool_wide_scratch_bytes(int R, int Ci, int Co, int npts);
 int sn_linear_forward_maxpool_wide(int R, int Ci, int Co, int npts, const float *ain, const float *coef_prev, const float *W,
@@ -353,7 +354,8 @@ int sn_pool_dgrad_sparse(int B, int npts, int Ci, int Co, const float *g, const 
  *                               three (a backward will read them) or none; z4 (R,128).  wplanes: 3 * 16384 bf16 for the split
  *                               weights (planes_ready != 0: already holds the split of these weights).  zero_keys / zero_n: optional
  *                               rider -- that many 64-bit words are cleared (the key scratch of the sn_linear_forward_maxpool
- *                               that follows). */
+ *                               that follows).  The entry runs any R >= 1 (rows at and beyond R are not written); _supported
+ *                               demands R % 64 == 0 only because the layer-by-layer route is bit-identical there alone. */
 int sn_pointnet_narrow_forward_supported(int R, int c1, int c2, int c3, int c4);
 int sn_pointnet_narrow_forward(int R, const float *x, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
                                const float *b3, const float *W4, const float *b4, void *wplanes, int planes_ready, float *z1, float *z2,

@@ -5,7 +5,8 @@ any device work.  So do the entries of include/samplenet_hip_internal.h that the
 (sn_skinny_linear, sn_skinny_linear2 -- which answer a size they do not serve with UNSUPPORTED --, sn_skinny_wgrad), the per-cloud
 transforms, the orthogonality regulariser and sn_bn_relu_*, and the nine entries of the one-batch task evaluation (cyclic padding, the
 valid-query Chamfer scan, the grouped Chamfer-mean loss, head + rotation plain and grouped), and the twelve entries of the sampler
-step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device), and the ten per-layer entries of the PointNet MLP (tests/test_gpu_mlp.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
+step's fused loss (the split pair scans, the step-loss forward / backward, the surface pair, the scalar loss entries), and the five FC-chain entries (tests/test_gpu_fc_chain.py calls them on a device), and the ten per-layer entries of the PointNet MLP (tests/test_gpu_mlp.py calls them on a device), and the five entries and two size queries of the
+registration task network's extractor (tests/test_gpu_task_net_direct.py calls them on a device).  The table below is the data; one child process (which sees no GPU, so that a call that slipped through a
 missing check comes back as an error code instead of touching a device with the made-up pointers) runs it once."""
 import ctypes
 
@@ -203,10 +204,29 @@ MLP = {
                               [3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16, 17, 19]),
 }
 
+# The registration task network's extractor entries (csrc/task_network.hip and sn_linear_forward_maxpool of csrc/pointnet_mlp.hip;
+# tests/test_gpu_task_net_direct.py calls them on a device): entry -> (valid argument list, positions of the REQUIRED pointers); optional
+# pointers are left NULL in the base.  The two narrow entries and the tile entry refuse a size below 1 as a BAD argument; the wide entry
+# and the sparse data gradient answer every size they do not serve -- negative ones included -- with UNSUPPORTED (callers ask their
+# `_supported` queries), after the pointer checks: every case is spelled out in _task_net_cases().
+TASK_NET = {
+    # R, Ci, Co, npts, ain, coef_prev, W, bias, z, keys, pooled, argsel, zsel, keys_cleared, stream
+    "sn_linear_forward_maxpool": ([128, 64, 64, 64, Pp, Pp, Pp, None, None, Pp, Pp, None, None, 0, None], [4, 5, 6, 9, 10]),
+    # R, Ci, Co, npts, ain, coef_prev, W, bias, z, scratch, pooled, argsel, zsel, wplanes, planes_ready, stream
+    "sn_linear_forward_maxpool_wide": ([16384, 64, 512, 64, Pp, None, Pp, None, None, Pp, Pp, None, None, Pp, 0, None], [4, 6, 9, 10, 13]),
+    # B, npts, Ci, Co, g, pooled, argsel, W, zprev, coef_prev, dyprev, stream
+    "sn_pool_dgrad_sparse": ([1, 8, 8, 8, Pp, Pp, Pp, Pp, None, None, Pp, None], [4, 5, 6, 7, 10]),
+    # R, x, W1, b1, W2, b2, W3, b3, W4, b4, wplanes, planes_ready, z1, z2, z3, z4, zero_keys, zero_n, stream
+    "sn_pointnet_narrow_forward": ([64, Pp, Pp, None, Pp, None, Pp, None, Pp, None, Pp, 0, None, None, None, Pp, None, 0, None],
+                                   [1, 2, 4, 6, 8, 10, 15]),
+    # R, dz4, z1, z2, z3, W1, W2, W3, W4, wplanes_t, planes_ready, dx, stream
+    "sn_pointnet_narrow_backward": ([64, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, Pp, 0, Pp, None], [1, 2, 3, 4, 5, 6, 7, 8, 9, 11]),
+}
+
 
 def _with(name, changes):
     args = list((ENTRIES.get(name) or INTERNAL.get(name) or TASK_BATCH.get(name) or STEP_LOSS.get(name) or SKINNY.get(name) or FC_CHAIN.get(name)
-                 or MLP[name])[0])
+                 or TASK_NET.get(name) or MLP[name])[0])
     for pos, val in changes.items():
         args[pos] = val
     return args
@@ -270,7 +290,45 @@ def _cases():
                      ("sn_grouping_operation_grad", {0: 0}), ("sn_grouping_operation_grad", {2: 0}),
                      ("sn_qrot_forward", {0: 0}), ("sn_qrot_forward", {1: 0}), ("sn_qrot_backward", {0: 0}), ("sn_nn_matching", {0: 0})):
         out.append(("%s-empty-%s" % (name, "".join("%d" % p for p in ch)), name, nulled(name, ch), 0, None))
-    return out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases() + _fc_chain_cases() + _mlp_cases()
+    return (out + _skinny_cases() + _transform_cases(nulled) + _task_batch_cases() + _step_loss_cases() + _fc_chain_cases() + _mlp_cases()
+            + _task_net_cases())
+
+
+def _task_net_cases():
+    out = []
+    add = lambda cid, name, ch, text=None, code=BAD: out.append(("%s-%s" % (name, cid), name, _with(name, ch), code, text or name))
+    for name, (base, required) in TASK_NET.items():
+        for pos in required:
+            add("arg%d-null" % pos, name, {pos: None})
+    tile, wide, sparse, nf, nb = TASK_NET
+    for pos in (0, 1, 2, 3):
+        add("size%d-negative" % pos, tile, {pos: -1}, "bad size")
+        add("size%d-zero" % pos, tile, {pos: 0}, "bad size")
+    # shapes the 64 x 64 tiles with one cloud per key do not serve: a single tile, clouds that are no multiple of 64 points or do not
+    # divide the rows, ragged channels
+    for cid, ch in (("R-64", {0: 64}), ("npts-32", {3: 32}), ("npts-96", {0: 192, 3: 96}), ("R-no-multiple-of-npts", {0: 192, 3: 128}),
+                    ("R-no-multiple-of-64", {0: 160, 3: 160}), ("Co-96", {2: 96}), ("Ci-40", {1: 40})):
+        add(cid, tile, ch, "needs 64-aligned rows per cloud / channels", UNSUP)
+    # the wide entry: fewer than 128 row blocks, rows that are no multiple of 128 / of the cloud, clouds that are no multiple of 32
+    # points, an input width other than 64 / 128, fewer than 512 or ragged output channels; a size below 1 is such a shape
+    for cid, ch in (("R-16256", {0: 16256}), ("R-16448", {0: 16448}), ("R-no-multiple-of-npts", {3: 96}), ("npts-16", {3: 16}),
+                    ("npts-48", {0: 16512, 3: 48}), ("Ci-32", {1: 32}), ("Ci-192", {1: 192}), ("Co-448", {2: 448}), ("Co-544", {2: 544}),
+                    ("R-negative", {0: -1}), ("Ci-zero", {1: 0}), ("Co-negative", {2: -1}), ("npts-zero", {3: 0}), ("npts-negative", {3: -32})):
+        add(cid, wide, ch, "needs R % 128 == 0", UNSUP)
+    add("R-16256-with-null-W", wide, {0: 16256, 6: None})  # (a NULL operand is BAD whatever the shape)
+    for pos in (0, 1, 2, 3):
+        for v in (0, -1):
+            add("size%d-is-%d" % (pos, v), sparse, {pos: v}, "at most 256 points per cloud", UNSUP)
+    add("npts-257", sparse, {1: 257}, "at most 256 points per cloud", UNSUP)
+    add("npts-257-with-null-g", sparse, {1: 257, 4: None})
+    for name in (nf, nb):
+        add("R-zero", name, {0: 0})
+        add("R-negative", name, {0: -1})
+    # z1..z3 of the forward: all three (a backward will read them) or none
+    for cid, ch in (("z1-alone", {12: Pp}), ("z2-alone", {13: Pp}), ("z3-alone", {14: Pp}), ("z1-z2", {12: Pp, 13: Pp}), ("z2-z3", {13: Pp, 14: Pp}),
+                    ("z1-z3", {12: Pp, 14: Pp})):
+        add(cid, nf, ch, "all three or none")
+    return out
 
 
 def _skinny_cases():
@@ -481,7 +539,8 @@ def _transform_cases(nulled):
 
 CASES = _cases()
 IN_SCOPE = sorted(ENTRIES) + sorted(INTERNAL) + sorted(TASK_BATCH) + sorted(STEP_LOSS) + sorted(SKINNY) + sorted(FC_CHAIN) + sorted(MLP) + ["sn_pairscan_workspace_bytes", "sn_soft_bwd_splits", "sn_skinny_linear_supported",
-                                               "sn_skinny_linear_scratch_bytes"]
+                                               "sn_skinny_linear_scratch_bytes"] + sorted(TASK_NET) + [
+                                                   "sn_linear_forward_maxpool_wide_supported", "sn_linear_forward_maxpool_wide_scratch_bytes"]
 
 
 @pytest.fixture(scope="module")
@@ -508,6 +567,12 @@ def test_the_table_walks_every_entry_in_scope():
         for pos, ty in enumerate(proto):
             assert (ty is ctypes.c_void_p) == (base[pos] in (Pp, None)), (name, pos)
             assert pos not in required or base[pos] == Pp, (name, pos)
+    for name, (base, required) in TASK_NET.items():
+        proto = _lib.PROTOTYPES[name]
+        assert len(base) == len(proto), name
+        for pos, ty in enumerate(proto[:-1]):  # (the last is the stream)
+            assert (ty is ctypes.c_void_p) == (base[pos] in (Pp, None)), (name, pos)
+            assert (pos in required) == (base[pos] == Pp), (name, pos)
     for name, (base, required, arrays) in FC_CHAIN.items():
         proto = _lib.PROTOTYPES[name]
         assert len(base) == len(proto) and set(arrays) <= set(required), name
