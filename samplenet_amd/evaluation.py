@@ -12,7 +12,8 @@ classifier's descriptors and rank and score all of them against each other in on
 The reference tests at batch_size 1 with an `.item()` per cloud and metric (main.py:128, 444-450).  Here a batch of any size goes
 through the same steps -- sampling, PCRNet, the pose-error terms, the Chamfer term, the sampling consistency -- with every value
 kept PER CLOUD on the device (ops.pose_errors, ops.chamfer_mean_per_cloud); `add` never synchronises and `result` makes one
-transfer.  With everything in eval mode a cloud's values do not depend on the clouds it is batched with.
+transfer.  With everything in eval mode a cloud's values do not depend on the clouds it is batched with.  How the columns lie in
+the one buffer that travels is known to _Collected.fetch alone: an evaluator names its columns and never counts an offset.
 """
 import numpy as np
 import torch
@@ -20,6 +21,46 @@ import torch
 from . import ops
 from .qtransform import qinv, rad_to_deg
 from .task_features import _igt_vec, qrot_cloud
+
+
+class _Collected:
+    """What an evaluator keeps on the device, one column per key, until the one transfer of result()."""
+
+    def __init__(self):
+        self._columns = {}  # key -> (numpy dtype of the fetched array, the device tensors put under the key)
+
+    def __bool__(self):
+        return bool(self._columns)
+
+    def put(self, key, tensor, dtype):
+        """Record a device tensor whose leading dimension is the item axis -- (B,), (B, 7), (B, M, 3), (1,) for a value per batch --
+        under `key` (any hashable); `dtype`: what fetch() returns the column as.  No device work, no synchronisation."""
+        self._columns.setdefault(key, (dtype, []))[1].append(tensor)
+
+    def on_device(self, key):
+        """the column's pieces as one device tensor, in the dtype they were put in"""
+        return torch.cat(self._columns[key][1])
+
+    def fetch(self):
+        """One torch.cat, one device-to-host transfer -> {key: array (items, *trailing)}, every array a copy of its own.  The
+        carrier is float32: counts, class and point indices are far below 2^24, so they cross it exactly."""
+        if not self._columns:
+            return {}
+        pieces = [p.reshape(-1).float() for _dtype, ps in self._columns.values() for p in ps]
+        flat = torch.cat(pieces).cpu().numpy()
+        out, o = {}, 0
+        for key, (dtype, ps) in self._columns.items():
+            shape = (sum(p.shape[0] for p in ps),) + tuple(ps[0].shape[1:])
+            size = sum(p.numel() for p in ps)
+            out[key] = flat[o:o + size].reshape(shape).astype(dtype)  # (astype copies: nothing keeps the carrier alive)
+            o += size
+        return out
+
+
+def _need_added(collected, owner):
+    if not collected:
+        raise RuntimeError("%s.result: nothing was added" % owner)
+    return collected
 
 
 def registration_aggregates(rotation_errors, trans_errs, consistency_errors, losses=None):
@@ -55,10 +96,10 @@ class RegistrationEvaluator:
             raise ValueError("RegistrationEvaluator: the task network must take (B,N,3) clouds (input_shape='bnc')")
         self.model, self.sampler = model, sampler
         self.num_sampled_clouds, self.loss_type = num_sampled_clouds, loss_type
-        self._rows = []  # (11, B) device tensors: rotation error [deg], translation error, consistency, loss, the estimated twist
+        self.reset()
 
     def reset(self):
-        self._rows = []
+        self._got = _Collected()
 
     def _sample(self, p):
         out = self.sampler(p)
@@ -66,39 +107,30 @@ class RegistrationEvaluator:
 
     def add(self, p0, p1, igt):
         """One batch: p0 template, p1 source (B,N,3) on the GPU, igt (B,7) or the reference's dict.  No synchronisation."""
-        if not (p0.is_cuda and p1.is_cuda):
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % p0.device)
-        model, sampler = self.model, self.sampler
-        states = [(m, m.training) for m in (model, sampler) if m is not None]
-        for m, _ in states:
-            m.eval()
-        try:
-            with torch.no_grad():
-                vec = _igt_vec(igt, p1).float().contiguous()
-                p0s, p1s = p0.contiguous(), p1.contiguous()
-                if sampler is not None:
-                    p1s = self._sample(p1s)
-                    if self.num_sampled_clouds == 2:
-                        p0s = self._sample(p0s)
-                twist, _pre, _qnorm, _quat, p1_est = model.forward_with_qnorm(p0s, p1s, rotate=p0s)
-                chamfer = ops.chamfer_mean_per_cloud(p1s, p1_est)
-                rot, nrm, trn = ops.pose_errors(twist, vec)
-                loss = nrm + chamfer if self.loss_type == 0 else chamfer
-                cons = ops.chamfer_mean_per_cloud(p0s, qrot_cloud(qinv(vec[:, 0:4]), p1s))  # (main.py:540-555)
-                self._rows.append(torch.cat([torch.stack([rad_to_deg(rot), trn, cons, loss]), twist.t()]))
-        finally:
-            for m, was in states:
-                m.train(was)
+        ops._need_gpu(p0, p1)
+        with _EvalMode(self.model, self.sampler), torch.no_grad():
+            vec = _igt_vec(igt, p1).float().contiguous()
+            p0s, p1s = p0.contiguous(), p1.contiguous()
+            if self.sampler is not None:
+                p1s = self._sample(p1s)
+                if self.num_sampled_clouds == 2:
+                    p0s = self._sample(p0s)
+            twist, _pre, _qnorm, _quat, p1_est = self.model.forward_with_qnorm(p0s, p1s, rotate=p0s)
+            chamfer = ops.chamfer_mean_per_cloud(p1s, p1_est)
+            rot, nrm, trn = ops.pose_errors(twist, vec)
+            cons = ops.chamfer_mean_per_cloud(p0s, qrot_cloud(qinv(vec[:, 0:4]), p1s))  # (main.py:540-555)
+            # (float64 is exact: what .item() returns per value)
+            self._got.put("rotation_errors", rad_to_deg(rot), np.float64)
+            self._got.put("trans_errs", trn, np.float64)
+            self._got.put("consistency_errors", cons, np.float64)
+            self._got.put("losses", nrm + chamfer if self.loss_type == 0 else chamfer, np.float64)
+            self._got.put("twists", twist, np.float64)
 
     def result(self):
         """One device-to-host transfer -> dict: the per-item arrays rotation_errors (degrees), trans_errs, consistency_errors,
         losses, twists (items, 7: the estimated poses, main.py:595's est_transform), and registration_aggregates of the first four."""
-        if not self._rows:
-            raise RuntimeError("RegistrationEvaluator.result: nothing was added")
-        table = torch.cat(self._rows, dim=1).cpu().numpy().astype(np.float64)  # (exact: what .item() returns per value)
-        out = {"rotation_errors": table[0], "trans_errs": table[1], "consistency_errors": table[2], "losses": table[3],
-               "twists": np.ascontiguousarray(table[4:11].T)}
-        out.update(registration_aggregates(table[0], table[1], table[2], table[3]))
+        out = _need_added(self._got, "RegistrationEvaluator").fetch()
+        out.update(registration_aggregates(out["rotation_errors"], out["trans_errs"], out["consistency_errors"], out["losses"]))
         return out
 
 
@@ -172,7 +204,7 @@ def classification_aggregates(preds, labels, batch_sizes, batch_losses, n_unique
 
 
 def _classify_batch(classifier, cloud, labels, reg_weight):
-    """One batch of one cloud size through the classifier: -> (logits, (3,B) rows pred / label / cross-entropy, loss_val (1,)) with
+    """One batch of one cloud size through the classifier: -> (logits, pred (B,) int32, cross-entropy (B,), loss_val (1,)) with
     loss_val = the batch's mean cross-entropy plus the weighted orthogonality term (evaluate_samplenet.py:236-241)."""
     from .classifier import orthogonality_loss
 
@@ -182,8 +214,7 @@ def _classify_batch(classifier, cloud, labels, reg_weight):
     t = end_points.get("transform")
     if t is not None:
         loss_val = loss_val + reg_weight * orthogonality_loss(t)
-    # (class indices and counts are far below 2^24: exact as float32)
-    return logits, torch.stack([pred.float(), labels.float(), ce]), loss_val.reshape(1)
+    return logits, pred, ce, loss_val.reshape(1)
 
 
 class ClassificationEvaluator:
@@ -198,44 +229,36 @@ class ClassificationEvaluator:
         self.reset()
 
     def reset(self):
-        self._rows, self._sizes, self._losses, self._logits, self._clouds = [], [], [], [], []
+        self._got, self._sizes = _Collected(), []
 
     def add(self, x, labels):
         """One batch: x (B,N,3) and labels (B,) integer class indices on the GPU.  No synchronisation."""
-        if not (x.is_cuda and labels.is_cuda):
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x, labels)
         with _EvalMode(self.classifier, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             simp, match, _idx, nun = _sample_with_indices(self.sampler, x)
             cloud = match if self.match_output else simp
-            logits, rows, loss_val = _classify_batch(self.classifier, cloud, labels, self.reg_weight)
-            self._rows.append(torch.cat([rows, nun.float().unsqueeze(0)]))
-            self._sizes.append(int(x.shape[0]))
-            self._losses.append(loss_val)
+            logits, pred, ce, loss_val = _classify_batch(self.classifier, cloud, labels, self.reg_weight)
+            self._got.put("preds", pred, np.int64)
+            self._got.put("labels", labels.clone(), np.int64)  # (a copy: the caller may refill its label buffer before result())
+            self._got.put("losses", ce, np.float64)
+            self._got.put("n_unique", nun, np.int64)
+            self._got.put("batch_losses", loss_val, np.float64)
+            # (without keep no logit travels: the empty slice carries the number of classes, which is host metadata)
+            self._got.put("logits", logits if self.keep else logits[:0], np.float32)
             if self.keep:
-                self._logits.append(logits.reshape(-1))
-                self._clouds.append(cloud.reshape(-1))
-            self._num_classes, self._cloud_points = int(logits.shape[1]), int(cloud.shape[1])
+                self._got.put("clouds", cloud, np.float32)
+            self._sizes.append(int(x.shape[0]))
 
     def result(self):
         """One device-to-host transfer -> dict: the per-item arrays preds, labels (int64), losses (float64: the cross-entropy per
         item), n_unique (int64); batch_sizes, batch_losses; classification_aggregates of them (avg_class_accuracy_seen is an addition
         to the reference's figures); with keep=True also logits (items, classes) and clouds (items, points, 3)."""
-        if not self._rows:
-            raise RuntimeError("ClassificationEvaluator.result: nothing was added")
-        n = sum(self._sizes)
-        flat = torch.cat([torch.cat(self._rows, dim=1).reshape(-1)] + self._losses + self._logits + self._clouds).cpu().numpy()
-        table = flat[:4 * n].reshape(4, n).astype(np.float64)
-        nb, C, M = len(self._sizes), self._num_classes, self._cloud_points
-        out = {"preds": table[0].astype(np.int64), "labels": table[1].astype(np.int64), "losses": table[2],
-               "n_unique": table[3].astype(np.int64), "batch_sizes": np.asarray(self._sizes, dtype=np.int64),
-               "batch_losses": flat[4 * n:4 * n + nb].astype(np.float64)}
-        if self.keep:
-            # (per batch the logits lie before the clouds' block: all logits first, then all clouds)
-            o = 4 * n + nb
-            out["logits"] = flat[o:o + n * C].reshape(n, C).copy()
-            out["clouds"] = flat[o + n * C:o + n * C + n * M * 3].reshape(n, M, 3).copy()
-        out.update(classification_aggregates(out["preds"], out["labels"], out["batch_sizes"], out["batch_losses"], out["n_unique"], C))
+        out = _need_added(self._got, "ClassificationEvaluator").fetch()
+        num_classes = (out["logits"] if self.keep else out.pop("logits")).shape[1]
+        out["batch_sizes"] = np.asarray(self._sizes, dtype=np.int64)
+        out.update(classification_aggregates(out["preds"], out["labels"], out["batch_sizes"], out["batch_losses"], out["n_unique"],
+                                             num_classes))
         return out
 
 
@@ -252,6 +275,13 @@ def reconstruction_aggregates(losses, reference_losses=None):
     return out
 
 
+def _per_cloud_loss(loss):
+    """the reconstruction loss by name -> the op (reconstruction, cloud) -> (B,) that computes it per cloud"""
+    if loss not in ("chamfer", "emd"):
+        raise ValueError("loss: 'chamfer' or 'emd'")
+    return ops.chamfer_mean_per_cloud if loss == "chamfer" else ops.emd_loss
+
+
 class ReconstructionEvaluator:
     """autoencoder: a PointNetAE; sampler as ClassificationEvaluator's (the matched points are reconstructed from); loss "chamfer"
     (ops.chamfer_mean_per_cloud) or "emd" (ops.emd_loss' per-cloud costs): get_loss_ae_per_pc (sampler_autoencoder.py:149-167: the
@@ -260,59 +290,38 @@ class ReconstructionEvaluator:
     keep: result() also returns sampled, sample_idx, reconstructions (the three arrays the reference script saves).  Clouds are (B,N,3)."""
 
     def __init__(self, autoencoder, sampler=None, loss="chamfer", with_reference=True, keep=False):
-        if loss not in ("chamfer", "emd"):
-            raise ValueError("loss: 'chamfer' or 'emd'")
+        self._per_cloud = _per_cloud_loss(loss)
         self.autoencoder, self.sampler = autoencoder, sampler
         self.loss, self.with_reference, self.keep = loss, bool(with_reference), bool(keep)
         self.reset()
 
     def reset(self):
-        self._rows, self._kept = [], []
-
-    def _per_cloud(self, recon, x):
-        if self.loss == "chamfer":
-            return ops.chamfer_mean_per_cloud(recon, x)
-        return ops.emd_loss(recon, x)
+        self._got = _Collected()
 
     def add(self, x):
         """One batch: x (B,N,3) on the GPU.  No synchronisation."""
-        if not x.is_cuda:
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x)
         ae = self.autoencoder
         with _EvalMode(ae, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             _simp, sampled, idx, nun = _sample_with_indices(self.sampler, x)
             recon = ae(_to_shape(sampled, ae)).contiguous()
-            loss = self._per_cloud(recon, x)
-            ref = self._per_cloud(ae(_to_shape(x, ae)).contiguous(), x) if self.with_reference else torch.zeros_like(loss)
-            self._rows.append(torch.stack([loss, ref, nun.float()]))
+            self._got.put("n_unique", nun, np.int64)
+            self._got.put("losses", self._per_cloud(recon, x), np.float64)
+            if self.with_reference:
+                self._got.put("reference_losses", self._per_cloud(ae(_to_shape(x, ae)).contiguous(), x), np.float64)
             if self.keep:
-                self._kept.append((sampled.reshape(-1), idx.float().reshape(-1), recon.reshape(-1)))
-            self._shape = (int(sampled.shape[1]), int(recon.shape[1]))
+                self._got.put("sampled", sampled, np.float32)
+                self._got.put("sample_idx", idx, np.int64)
+                self._got.put("reconstructions", recon, np.float32)
 
     def result(self):
         """One device-to-host transfer -> dict: the per-item float64 arrays losses, n_unique (int64) and, with_reference,
         reference_losses and nre (their quotient, np.divide as the reference); mean_loss, mean_unique, mean_reference_loss, mean_nre
         (evaluate_samplenet.py:143, 151-152); with keep=True sampled (items, M, 3), sample_idx (items, M) int64, reconstructions."""
-        if not self._rows:
-            raise RuntimeError("ReconstructionEvaluator.result: nothing was added")
-        sizes = [r.shape[1] for r in self._rows]
-        n = sum(sizes)
-        parts = [torch.cat(self._rows, dim=1).reshape(-1)]
-        for k in range(3):
-            parts += [kept[k] for kept in self._kept]
-        flat = torch.cat(parts).cpu().numpy()
-        table = flat[:3 * n].reshape(3, n).astype(np.float64)
-        out = {"n_unique": table[2].astype(np.int64), "mean_unique": float(table[2].mean())}
-        out.update(reconstruction_aggregates(table[0], table[1] if self.with_reference else None))
-        if self.keep:
-            M, R = self._shape
-            o = 3 * n
-            out["sampled"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
-            o += n * M * 3
-            out["sample_idx"] = flat[o:o + n * M].astype(np.int64).reshape(n, M)
-            o += n * M
-            out["reconstructions"] = flat[o:o + n * R * 3].reshape(n, R, 3).copy()
+        out = _need_added(self._got, "ReconstructionEvaluator").fetch()
+        out["mean_unique"] = float(out["n_unique"].mean())  # (integers: their float64 mean, whatever the order of the sum)
+        out.update(reconstruction_aggregates(out["losses"], out.get("reference_losses")))
         return out
 
 
@@ -376,62 +385,46 @@ class ProgressiveClassificationEvaluator:
         self.reset()
 
     def reset(self):
-        self._rows = {s: [] for s in self.sizes}    # (3, B): pred, label, cross-entropy
-        self._losses = {s: [] for s in self.sizes}
-        self._logits = {s: [] for s in self.sizes}
-        self._unique, self._batch, self._ranked = [], [], []
+        self._got, self._batch = _Collected(), []
 
     def add(self, x, labels):
         """One batch: x (B,N,3) and labels (B,) on the GPU: ranked once, classified once per size.  No synchronisation."""
-        if not (x.is_cuda and labels.is_cuda):
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x, labels)
         with _EvalMode(self.classifier, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             ordered, order, nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
             for s in self.sizes:
-                logits, rows, loss_val = _classify_batch(self.classifier, ordered[:, :s].contiguous(), labels, self.reg_weight)
-                self._rows[s].append(rows)
-                self._losses[s].append(loss_val)
-                if self.keep:
-                    self._logits[s].append(logits.reshape(-1))
-                self._num_classes = int(logits.shape[1])
-            self._unique.append(nun.float())
+                logits, pred, ce, loss_val = _classify_batch(self.classifier, ordered[:, :s].contiguous(), labels, self.reg_weight)
+                self._got.put(("preds", s), pred, np.int64)
+                self._got.put(("losses", s), ce, np.float64)
+                self._got.put(("batch_losses", s), loss_val, np.float64)
+                self._got.put(("logits", s), logits if self.keep else logits[:0], np.float32)  # (as ClassificationEvaluator.add)
+            self._got.put("labels", labels.clone(), np.int64)  # (a copy, as there)
+            self._got.put("n_unique", nun, np.int64)
             self._batch.append(int(x.shape[0]))
             if self.keep:
-                self._ranked.append((ordered.reshape(-1), order.float().reshape(-1)))  # (indices are below 2^24: exact)
+                self._got.put("ordered", ordered, np.float32)
+                self._got.put("order", order, np.int64)
 
     def result(self):
         """One device-to-host transfer -> {"sizes", "n_unique" (items,) int64, "mean_unique", "by_size": {s: ...}}: by_size[s] holds
         what ClassificationEvaluator.result() holds for the first s ranked points (preds, labels, losses, batch_sizes, batch_losses,
         classification_aggregates of them) except the unique counts, which belong to the ranking; with keep=True by_size[s]["logits"]
         and, at the top, "ordered" (items, max size, 3) and "order" (items, max size) int64."""
-        if not self._batch:
-            raise RuntimeError("ProgressiveClassificationEvaluator.result: nothing was added")
-        n, nb, C, M = sum(self._batch), len(self._batch), self._num_classes, self.sizes[-1]
-        parts = [torch.cat(self._unique)]
-        for s in self.sizes:
-            parts += [torch.cat(self._rows[s], dim=1).reshape(-1)] + self._losses[s] + self._logits[s]
-        for k in range(2):
-            parts += [r[k] for r in self._ranked]
-        flat = torch.cat(parts).cpu().numpy()
-        n_unique, o = flat[:n].astype(np.int64), n
+        got = _need_added(self._got, "ProgressiveClassificationEvaluator").fetch()
         batch_sizes = np.asarray(self._batch, dtype=np.int64)
-        out = {"sizes": list(self.sizes), "n_unique": n_unique, "by_size": {}}
+        out = {"sizes": list(self.sizes), "n_unique": got["n_unique"], "by_size": {}}
         for s in self.sizes:
-            table = flat[o:o + 3 * n].reshape(3, n).astype(np.float64)
-            o += 3 * n
-            r = {"preds": table[0].astype(np.int64), "labels": table[1].astype(np.int64), "losses": table[2],
-                 "batch_sizes": batch_sizes, "batch_losses": flat[o:o + nb].astype(np.float64)}
-            o += nb
+            r = {"preds": got["preds", s], "labels": got["labels"], "losses": got["losses", s], "batch_sizes": batch_sizes,
+                 "batch_losses": got["batch_losses", s]}
             if self.keep:
-                r["logits"] = flat[o:o + n * C].reshape(n, C).copy()
-                o += n * C
-            r.update(classification_aggregates(r["preds"], r["labels"], batch_sizes, r["batch_losses"], n_unique, C))
+                r["logits"] = got["logits", s]
+            r.update(classification_aggregates(r["preds"], r["labels"], batch_sizes, r["batch_losses"], out["n_unique"],
+                                               got["logits", s].shape[1]))
             out["mean_unique"] = r.pop("mean_unique")  # (the ranking's, the same at every size)
             out["by_size"][s] = r
         if self.keep:
-            out["ordered"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
-            out["order"] = flat[o + n * M * 3:o + n * M * 4].astype(np.int64).reshape(n, M)
+            out["ordered"], out["order"] = got["ordered"], got["order"]
         return out
 
 
@@ -441,66 +434,47 @@ class ProgressiveReconstructionEvaluator:
     is computed once per batch, the nre per size; sampler, sizes: as ProgressiveClassificationEvaluator.  Clouds are (B,N,3)."""
 
     def __init__(self, autoencoder, sampler, sizes=None, loss="chamfer", with_reference=True, keep=False):
-        if loss not in ("chamfer", "emd"):
-            raise ValueError("loss: 'chamfer' or 'emd'")
+        self._per_cloud = _per_cloud_loss(loss)
         self.autoencoder, self.sampler = autoencoder, sampler
         self.sizes = _default_sizes(sampler, sizes)
         self.loss, self.with_reference, self.keep = loss, bool(with_reference), bool(keep)
         self.reset()
 
     def reset(self):
-        self._losses = {s: [] for s in self.sizes}
-        self._recons = {s: [] for s in self.sizes}
-        self._shared, self._batch, self._ranked = [], [], []  # _shared: (2, B) reference loss, n_unique
-
-    _per_cloud = ReconstructionEvaluator._per_cloud
+        self._got = _Collected()
 
     def add(self, x):
         """One batch: x (B,N,3) on the GPU: ranked once, reconstructed once per size.  No synchronisation."""
-        if not x.is_cuda:
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x)
         ae = self.autoencoder
         with _EvalMode(ae, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             ordered, order, nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
             for s in self.sizes:
                 recon = ae(_to_shape(ordered[:, :s].contiguous(), ae)).contiguous()
-                self._losses[s].append(self._per_cloud(recon, x))
+                self._got.put(("losses", s), self._per_cloud(recon, x), np.float64)
                 if self.keep:
-                    self._recons[s].append(recon.reshape(-1))
-                self._recon_points = int(recon.shape[1])
-            ref = self._per_cloud(ae(_to_shape(x, ae)).contiguous(), x) if self.with_reference else torch.zeros_like(nun, dtype=torch.float32)
-            self._shared.append(torch.stack([ref, nun.float()]))
-            self._batch.append(int(x.shape[0]))
+                    self._got.put(("reconstructions", s), recon, np.float32)
+            if self.with_reference:
+                self._got.put("reference_losses", self._per_cloud(ae(_to_shape(x, ae)).contiguous(), x), np.float64)
+            self._got.put("n_unique", nun, np.int64)
             if self.keep:
-                self._ranked.append((ordered.reshape(-1), order.float().reshape(-1)))
+                self._got.put("ordered", ordered, np.float32)
+                self._got.put("order", order, np.int64)
 
     def result(self):
         """One device-to-host transfer -> {"sizes", "n_unique", "mean_unique", "by_size": {s: reconstruction_aggregates (losses,
         mean_loss and, with_reference, reference_losses -- the same array at every size --, nre, mean_reference_loss, mean_nre)}};
         with keep=True by_size[s]["reconstructions"] and, at the top, "ordered" and "order" (int64)."""
-        if not self._batch:
-            raise RuntimeError("ProgressiveReconstructionEvaluator.result: nothing was added")
-        n, M = sum(self._batch), self.sizes[-1]
-        parts = [torch.cat(self._shared, dim=1).reshape(-1)]
+        got = _need_added(self._got, "ProgressiveReconstructionEvaluator").fetch()
+        out = {"sizes": list(self.sizes), "n_unique": got["n_unique"], "mean_unique": float(got["n_unique"].mean()), "by_size": {}}
         for s in self.sizes:
-            parts += self._losses[s] + self._recons[s]
-        for k in range(2):
-            parts += [r[k] for r in self._ranked]
-        flat = torch.cat(parts).cpu().numpy()
-        shared, o = flat[:2 * n].reshape(2, n).astype(np.float64), 2 * n
-        out = {"sizes": list(self.sizes), "n_unique": shared[1].astype(np.int64), "mean_unique": float(shared[1].mean()), "by_size": {}}
-        for s in self.sizes:
-            r = reconstruction_aggregates(flat[o:o + n].astype(np.float64), shared[0] if self.with_reference else None)
-            o += n
+            r = reconstruction_aggregates(got["losses", s], got.get("reference_losses"))
             if self.keep:
-                R = self._recon_points
-                r["reconstructions"] = flat[o:o + n * R * 3].reshape(n, R, 3).copy()
-                o += n * R * 3
+                r["reconstructions"] = got["reconstructions", s]
             out["by_size"][s] = r
         if self.keep:
-            out["ordered"] = flat[o:o + n * M * 3].reshape(n, M, 3).copy()
-            out["order"] = flat[o + n * M * 3:o + n * M * 4].astype(np.int64).reshape(n, M)
+            out["ordered"], out["order"] = got["ordered"], got["order"]
         return out
 
 
@@ -536,39 +510,33 @@ class RetrievalEvaluator:
         self.reset()
 
     def reset(self):
-        self._desc, self._labels = [], []
+        self._kept = _Collected()  # (result() takes these columns on the device, scores them there and fetches the scores)
 
     def add(self, x, labels):
         """One batch: x (B,N,3) and labels (B,) integer class indices on the GPU.  No synchronisation."""
-        if not (x.is_cuda and labels.is_cuda):
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x, labels)
         with _EvalMode(self.classifier, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             simp, match, _idx, _nun = _sample_with_indices(self.sampler, x)
-            self._desc.append(_descriptors(self.classifier, match if self.match_output else simp))
-            self._labels.append(labels.reshape(-1).int())
+            self._kept.put("descriptors", _descriptors(self.classifier, match if self.match_output else simp), np.float32)
+            self._kept.put("labels", labels.reshape(-1).int(), np.int64)
 
     def result(self):
         """One launch and one device-to-host transfer -> dict: the per-query arrays ap (float64; NaN for a query without a relevant
         shape), prec (items, levels), n_relevant, labels (int64), retrieval_aggregates of them (map, pr_curve, auc, n_valid); with
         keep=True also descriptors (items, C) float32 and order (items, items - 1) int64, the ranking of every query."""
-        if not self._desc:
-            raise RuntimeError("RetrievalEvaluator.result: nothing was added")
-        desc, labels = torch.cat(self._desc), torch.cat(self._labels)
-        n, C, L = desc.shape[0], desc.shape[1], self.levels
-        got = ops.retrieval_metrics(desc, labels, L, return_order=self.keep)
-        # (counts, class indices and shape indices are far below 2^24: exact as float32)
-        parts = [got[0], got[1].reshape(-1), got[2].float(), labels.float()]
+        kept = _need_added(self._kept, "RetrievalEvaluator")
+        desc, labels = kept.on_device("descriptors"), kept.on_device("labels")
+        scored = ops.retrieval_metrics(desc, labels, self.levels, return_order=self.keep)
+        got = _Collected()
+        got.put("ap", scored[0], np.float64)
+        got.put("prec", scored[1], np.float64)
+        got.put("n_relevant", scored[2], np.int64)
+        got.put("labels", labels, np.int64)
         if self.keep:
-            parts += [desc.reshape(-1), got[3].float().reshape(-1)]
-        flat = torch.cat(parts).cpu().numpy()
-        o = n * (L + 1)
-        out = {"ap": flat[:n].astype(np.float64), "prec": flat[n:o].reshape(n, L).astype(np.float64),
-               "n_relevant": flat[o:o + n].astype(np.int64), "labels": flat[o + n:o + 2 * n].astype(np.int64)}
-        if self.keep:
-            o += 2 * n
-            out["descriptors"] = flat[o:o + n * C].reshape(n, C).copy()
-            out["order"] = flat[o + n * C:].astype(np.int64).reshape(n, max(n - 1, 0))
+            got.put("descriptors", desc, np.float32)
+            got.put("order", scored[3], np.int64)
+        out = got.fetch()
         out.update(retrieval_aggregates(out["ap"], out["prec"], out["n_relevant"]))
         return out
 
@@ -585,37 +553,34 @@ class ProgressiveRetrievalEvaluator:
         self.reset()
 
     def reset(self):
-        self._desc = {s: [] for s in self.sizes}
-        self._labels = []
+        self._kept = _Collected()  # (as RetrievalEvaluator's)
 
     def add(self, x, labels):
         """One batch: x (B,N,3) and labels (B,) on the GPU: ranked once, described once per size.  No synchronisation."""
-        if not (x.is_cuda and labels.is_cuda):
-            raise RuntimeError("samplenet_amd ops run on the GPU only (got a %s tensor); no CPU fallback exists" % x.device)
+        ops._need_gpu(x, labels)
         with _EvalMode(self.classifier, self.sampler), torch.no_grad():
             x = x.contiguous().float()
             ordered, _order, _nun = _ranked_cloud(self.sampler, x, self.sizes[-1])
             for s in self.sizes:
-                self._desc[s].append(_descriptors(self.classifier, ordered[:, :s].contiguous()))
-            self._labels.append(labels.reshape(-1).int())
+                self._kept.put(("descriptors", s), _descriptors(self.classifier, ordered[:, :s].contiguous()), np.float32)
+            self._kept.put("labels", labels.reshape(-1).int(), np.int64)
 
     def result(self):
         """One launch for all sizes and one device-to-host transfer -> {"sizes", "labels", "n_relevant" (the labels alone decide
         it: the same at every size), "by_size": {s: ap, prec, retrieval_aggregates of them}}."""
-        if not self._labels:
-            raise RuntimeError("ProgressiveRetrievalEvaluator.result: nothing was added")
-        desc = torch.stack([torch.cat(self._desc[s]) for s in self.sizes])
-        labels = torch.cat(self._labels)
-        S, n, L = desc.shape[0], desc.shape[1], self.levels
-        ap, prec, n_relevant = ops.retrieval_metrics(desc, labels, L)
-        flat = torch.cat([ap.reshape(-1), prec.reshape(-1), n_relevant.float(), labels.float()]).cpu().numpy()
-        aps = flat[:S * n].reshape(S, n).astype(np.float64)
-        precs = flat[S * n:S * n * (L + 1)].reshape(S, n, L).astype(np.float64)
-        o = S * n * (L + 1)
-        out = {"sizes": list(self.sizes), "n_relevant": flat[o:o + n].astype(np.int64), "labels": flat[o + n:].astype(np.int64),
-               "by_size": {}}
+        kept = _need_added(self._kept, "ProgressiveRetrievalEvaluator")
+        labels = kept.on_device("labels")
+        ap, prec, n_relevant = ops.retrieval_metrics(torch.stack([kept.on_device(("descriptors", s)) for s in self.sizes]), labels,
+                                                     self.levels)
+        got = _Collected()  # (ap (sizes, items) and prec (sizes, items, levels): here a size is an item of the column)
+        got.put("ap", ap, np.float64)
+        got.put("prec", prec, np.float64)
+        got.put("n_relevant", n_relevant, np.int64)
+        got.put("labels", labels, np.int64)
+        got = got.fetch()
+        out = {"sizes": list(self.sizes), "n_relevant": got["n_relevant"], "labels": got["labels"], "by_size": {}}
         for k, s in enumerate(self.sizes):
-            r = {"ap": aps[k], "prec": precs[k]}
-            r.update(retrieval_aggregates(aps[k], precs[k], out["n_relevant"]))
+            r = {"ap": got["ap"][k], "prec": got["prec"][k]}
+            r.update(retrieval_aggregates(r["ap"], r["prec"], out["n_relevant"]))
             out["by_size"][s] = r
         return out

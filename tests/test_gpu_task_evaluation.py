@@ -182,6 +182,67 @@ def test_reconstruction_evaluator(samp_kind, loss):
         assert np.array_equal(res["losses"], res["reference_losses"]) and (res["nre"] == 1).all()
 
 
+def _sync_warnings(fn):
+    """fn() under torch's "warn" sync-debug mode -> (its value, how many synchronising calls torch reported)"""
+    import warnings
+
+    torch.cuda.synchronize()
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        torch.cuda.set_sync_debug_mode("warn")
+        try:
+            value = fn()
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+    # (torch's own once-only notice that the mode is a prototype speaks of synchronising too: only the per-call report counts)
+    return value, sum("called a synchronizing" in str(w.message) for w in caught)
+
+
+def test_result_makes_one_synchronising_call(monkeypatch):
+    """result() of each of the seven evaluators, keep=True where it exists, after batches of 5, 4 and 3: exactly ONE synchronising
+    call, the transfer.  Counted by torch's sync-debug mode "warn", after checking on a plain .cpu() of a device tensor that this
+    torch build reports a blocking device-to-host copy there, once (it does on the ROCm build this was written on; a build that
+    does not has the calls of torch.Tensor.cpu counted instead)."""
+    from samplenet_amd import (ClassificationEvaluator, PointNetAE, ProgressiveClassificationEvaluator,
+                               ProgressiveReconstructionEvaluator, ProgressiveRetrievalEvaluator, ReconstructionEvaluator,
+                               RegistrationEvaluator, RetrievalEvaluator, SampleNetProgressive)
+    from samplenet_amd.task_features import PCRNet
+
+    x, labels = _data()
+    g = torch.Generator().manual_seed(3)
+    quat = torch.randn(ITEMS, 4, generator=g)
+    igt = torch.cat([quat / quat.norm(dim=1, keepdim=True), torch.zeros(ITEMS, 3)], dim=1).cuda()
+    classifier, sampler = _classifier("full"), _sampler("samplenet")
+    torch.manual_seed(6)
+    ae = PointNetAE(n_pc_points=N, bottleneck_size=128, input_shape="bnc").cuda().eval()
+    pcr = PCRNet(bottleneck_size=256, input_shape="bnc").cuda().eval()
+    ranker = SampleNetProgressive((8, M), 128, group_size=4, input_shape="bnc", output_shape="bnc").cuda().eval()
+    cases = [(RegistrationEvaluator(pcr, sampler), (x, x.flip(1).contiguous(), igt)),
+             (ClassificationEvaluator(classifier, sampler, keep=True), (x, labels)),
+             (ReconstructionEvaluator(ae, sampler, keep=True), (x,)),
+             (ProgressiveClassificationEvaluator(classifier, ranker, keep=True), (x, labels)),
+             (ProgressiveReconstructionEvaluator(ae, ranker, keep=True), (x,)),
+             (RetrievalEvaluator(classifier, sampler, keep=True), (x, labels)),
+             (ProgressiveRetrievalEvaluator(classifier, ranker), (x, labels))]
+    for ev, tensors in cases:
+        for lo, hi in zip(CUTS[:-1], CUTS[1:]):
+            ev.add(*[t[lo:hi] for t in tensors])
+
+    _, reported = _sync_warnings(lambda: torch.ones(1, device="cuda").cpu())
+    print("EVAL_SYNC a plain .cpu(): %d synchronising call(s) reported by the sync-debug mode" % reported)
+    calls = []
+    if reported != 1:
+        to_host = torch.Tensor.cpu
+        monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **k: calls.append(1) or to_host(self, *a, **k))
+    for ev, _ in cases:
+        del calls[:]
+        res, warned = _sync_warnings(ev.result)
+        count = warned if reported == 1 else len(calls)
+        print("EVAL_SYNC %-36s %d synchronising call(s)" % (type(ev).__name__, count))
+        assert count == 1, type(ev).__name__
+        assert len(res["labels" if "labels" in res else "n_unique" if "n_unique" in res else "losses"]) == ITEMS
+
+
 def test_result_before_add_raises_and_argument_checks():
     from samplenet_amd import ClassificationEvaluator, PointNetAE, ReconstructionEvaluator
 
