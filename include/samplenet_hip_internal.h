@@ -839,6 +839,52 @@ int sn_gather_invert(int b, int n, int ne, const int *idx, int *start, int *orde
 int sn_weighted_gather_backward_inverted(int b, int c, int n, int m, int k, const float *weights, const float *grad_out,
                                          const int *start, const int *order, float *grad_X, sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * A PointNet++ set-abstraction level around the GEMM entries above (csrc/set_abstraction.hip; restated in numpy by
+ * tests/group_rows_ref.py): the grouped points in the ROW layout the GEMMs read, the gradient of that gather by inverted index, and
+ * a max-pool pair for many small groups.  Together the first two replace query_ball_point_gpu + group_point_gpu +
+ * group_point_grad_gpu (tf_grouping_g.cu:3-36, 40-57, 61-78) and the centre subtraction, on that layout.
+ *
+ * sn_ball_group_rows_forward: xyz (b,n,3), new_xyz (b,m,3), features (b,n,c) ROW-major (channels contiguous) or NULL with c == 0;
+ *   rows (b, m, nsample, 3 use_xyz + c): with use_xyz, columns 0..2 of row (j,s) are xyz[idx[j,s]] - new_xyz[j] (one fp32 subtraction
+ *   each), then the c feature columns of point idx[j,s].  idx / pts_cnt are written exactly as by sn_ball_query (pts_cnt may be
+ *   NULL; an empty ball groups point 0).  Bit-identical to sn_ball_group_forward's output permuted.  One launch, no workspace, no
+ *   atomics, capturable.  Checked on the host before any device work, as sn_ball_group_forward: a negative size, nsample < 1, an
+ *   unknown rule / use_xyz, c == 0 without use_xyz -> SN_ERR_BAD_ARGUMENT; b == 0 or m == 0 is a no-op that succeeds; n == 0 with
+ *   b * m > 0, a NULL required pointer -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1 workgroups -> SN_ERR_UNSUPPORTED.
+ *
+ * sn_group_rows_backward: grad_rows (b, m*nsample, 3 use_xyz + c); start (b,n+1) / order (b, m*nsample) from
+ *   sn_gather_invert(b, n, m*nsample, idx, ..).  idx itself is not read (the lists carry all it says) and may be NULL.  Each output
+ *   may be NULL; one that is NULL is not touched, the others are OVERWRITTEN:
+ *   grad_features (b,n,c), grad_xyz (b,n,3): element [b,r,ch] = the fp32 sum, from +0, over i in [start[b,r], start[b,r+1]) in that
+ *       order (ascending entry number) of grad_rows[b, order[b,i], col]; every add rounded, nothing contracted; a row with an empty
+ *       list gets +0.  No atomics, one order: the bits repeat.  A start outside [0, m*nsample] is clamped and an entry number outside
+ *       [0, m*nsample) skipped.  KNOWN LIMIT: lists are not split, so a launch takes as long as its longest list -- and point 0
+ *       collects every empty ball;
+ *   grad_new_xyz (b,m,3): -(sum over s of grad_rows[b, j*nsample + s, 0:3]) in sn_ball_group_backward's order (lane l adds slots l,
+ *       l + 64, .. ascending, the xor tree 32 .. 1, one negation): bit-identical to that entry on the permuted gradient.
+ *   Without use_xyz the two point gradients are zeros.  Up to two launches, no workspace, capturable.  Checked on the host: a
+ *   negative size, nsample < 1, an unknown use_xyz, c == 0 without use_xyz, m * nsample beyond 2^31 - 1 -> SN_ERR_BAD_ARGUMENT;
+ *   b == 0 is a no-op that succeeds; grad_rows NULL with m > 0, or start (order with m > 0) NULL when grad_features / grad_xyz is
+ *   asked for -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1 workgroups -> SN_ERR_UNSUPPORTED.
+ *
+ * sn_group_pool_forward: sn_pool_forward(B = G, N = S, ..) bit for bit (per channel max or min by the sign of the scale, the FIRST
+ *   row wins a tie, pooled = relu(scale * z + shift) as one fmaf), for many small groups: a wave per (group, 64 channels).
+ * sn_group_pool_backward: gsel = g * [pooled > 0], bit for bit sn_pool_backward's, and -- unless stats is NULL -- the
+ *   BatchNorm-backward partial sums stats [nblk][2][C], nblk = sn_group_pool_stats_blocks(G): block k holds (sum gsel, sum
+ *   fl(gsel * zsel)) over groups 64 k .. 64 k + 63, slice q of four adding groups q, q + 4, .. ascending and the four slice sums added
+ *   in slice order: the layout sn_bn_backward_coef(nblk, C, R, stats, ..) reduces.  On fixed statistics the caller forms
+ *   kcoef = (scale, 0, 0) itself.  Both: one launch, G, S, C >= 1 and non-NULL pointers or SN_ERR_BAD_ARGUMENT. */
+int sn_ball_group_rows_forward(int b, int n, int m, int c, float radius, int nsample, int rule, int use_xyz, const float *xyz,
+                               const float *new_xyz, const float *features, int *idx, int *pts_cnt, float *rows, sn_stream_t stream);
+int sn_group_rows_backward(int b, int n, int m, int c, int nsample, int use_xyz, const int *idx, const int *start, const int *order,
+                           const float *grad_rows, float *grad_features, float *grad_xyz, float *grad_new_xyz, sn_stream_t stream);
+int sn_group_pool_forward(int G, int S, int C, const float *z, const float *coef, float *pooled, int *argsel, float *zsel,
+                          sn_stream_t stream);
+int sn_group_pool_stats_blocks(int G);
+int sn_group_pool_backward(int G, int C, const float *g, const float *pooled, const float *zsel, float *gsel, float *stats,
+                           sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -750,6 +750,78 @@ def three_interpolate(features, idx, weight, inverse=None):
     return ThreeInterpolateFunction.apply(features, idx, weight, start, order)
 
 
+# --------------------------------------------------------------------------------------------- set abstraction: row-layout grouping
+class BallGroupRowsFunction(torch.autograd.Function):
+    """xyz (B,N,3), new_xyz (B,M,3), features (B,N,C) row-major or None -> rows (B, M, nsample, 3 use_xyz + C), idx, pts_cnt
+    (sn_ball_group_rows_forward).  Backward: sn_gather_invert + sn_group_rows_backward, only the outputs that need a gradient;
+    beyond sn_gather_invert_supported the gradient is permuted to channel-major for sn_ball_group_backward (float atomics)."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, features, radius, nsample, use_xyz, rule):
+        _need_gpu(xyz, new_xyz, features)
+        xyz, new_xyz = _f32c(xyz), _f32c(new_xyz)
+        features = None if features is None else _f32c(features)
+        if xyz.dim() != 3 or xyz.shape[2] != 3 or new_xyz.dim() != 3 or new_xyz.shape[2] != 3 or new_xyz.shape[0] != xyz.shape[0]:
+            raise ValueError("ball_group_rows: xyz must be (B,N,3) and new_xyz (B,M,3)")
+        b, n, _ = xyz.shape
+        m = new_xyz.shape[1]
+        if features is not None and (features.dim() != 3 or features.shape[0] != b or features.shape[1] != n):
+            raise ValueError("ball_group_rows: features_bnc must be (B,N,C)")
+        c = 0 if features is None else features.shape[2]
+        u = 1 if use_xyz else 0
+        rows = torch.empty(b, m, nsample, 3 * u + c, device=xyz.device, dtype=torch.float32)
+        idx = torch.empty(b, m, nsample, device=xyz.device, dtype=torch.int32)
+        cnt = torch.empty(b, m, device=xyz.device, dtype=torch.int32)
+        with torch.cuda.device(xyz.device):
+            check(lib.sn_ball_group_rows_forward(b, n, m, c, float(radius), nsample, rule, u, ptr(xyz), ptr(new_xyz), ptr(features),
+                                                 ptr(idx), ptr(cnt), ptr(rows), _stream(xyz)), "sn_ball_group_rows_forward")
+        ctx.save_for_backward(idx)
+        ctx.dims = (b, n, m, c, nsample, u)
+        ctx.mark_non_differentiable(idx, cnt)
+        return rows, idx, cnt
+
+    @staticmethod
+    def backward(ctx, grad_rows, _gi, _gc):
+        (idx,) = ctx.saved_tensors
+        b, n, m, c, ns, u = ctx.dims
+        grad_rows = _f32c(grad_rows)
+        dev = grad_rows.device
+        need_xyz, need_new, need_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and c > 0
+        gx = torch.empty(b, n, 3, device=dev, dtype=torch.float32) if need_xyz else None
+        gn = torch.empty(b, m, 3, device=dev, dtype=torch.float32) if need_new else None
+        with torch.cuda.device(dev):
+            st = _stream(grad_rows)
+            if (need_xyz or need_f) and not gather_invert_supported(n, m * ns):
+                # the atomic route: sn_ball_group_backward reads channel-major and writes (B,C,N)
+                g = grad_rows.permute(0, 3, 1, 2).contiguous()
+                gf = torch.empty(b, c, n, device=dev, dtype=torch.float32) if need_f else None
+                check(lib.sn_ball_group_backward(b, n, m, c, ns, u, ptr(idx), ptr(g), ptr(gf), ptr(gx), ptr(gn), st),
+                      "sn_ball_group_backward")
+                return gx, gn, (gf.transpose(1, 2).contiguous() if need_f else None), None, None, None, None
+            gf = torch.empty(b, n, c, device=dev, dtype=torch.float32) if need_f else None
+            start = order = None
+            if (need_xyz and u) or need_f:
+                start, order = gather_invert(idx, n)
+            check(lib.sn_group_rows_backward(b, n, m, c, ns, u, ptr(idx), ptr(start), ptr(order), ptr(grad_rows), ptr(gf), ptr(gx),
+                                             ptr(gn), st), "sn_group_rows_backward")
+        return gx, gn, gf, None, None, None, None
+
+
+def ball_group_rows(radius, nsample, xyz, new_xyz, features_bnc=None, use_xyz=True, rule="squared", return_idx=False):
+    """QueryAndGroup in the row layout the GEMM entries read: xyz (B,N,3), new_xyz (B,M,3), features_bnc (B,N,C) ROW-major or None
+    -> rows (B, M, nsample, 3 use_xyz + C): with use_xyz the first three columns are xyz[idx] - new_xyz, then the C feature columns
+    of point idx, idx the ball query's rows (ops.ball_query) -- ops.ball_group's tensor permuted, bit for bit, in one launch.
+    Gradients reach features_bnc, xyz and new_xyz where each requires one.  Within ops.gather_invert_supported(N, M * nsample) the
+    gradients towards features_bnc and xyz are DETERMINISTIC: per point the sum over the slots that name it in ascending slot order,
+    by inverted index (a launch takes as long as its longest list; point 0 collects every empty ball).  Beyond that bound they take
+    sn_ball_group_backward's route on the permuted gradient, which sums with float atomics (last bits depend on arrival order).
+    The gradient towards new_xyz has one order on both routes.  return_idx: also the indices (B,M,nsample) and counts (B,M)."""
+    if features_bnc is None and not use_xyz:
+        raise ValueError("ball_group_rows: nothing to group (features_bnc is None and use_xyz is False)")
+    rows, idx, cnt = BallGroupRowsFunction.apply(xyz, new_xyz, features_bnc, radius, nsample, bool(use_xyz), _ball_rule(rule))
+    return (rows, idx, cnt) if return_idx else rows
+
+
 # --------------------------------------------------------------------------------------------- SoftProjection
 def _grad_temperature(gsig, temperature, min_sigma):
     """d loss / dT from the d loss / d sigma partials (one tiny kernel): sigma = max(T^2, min_sigma), with torch.max's
