@@ -6,8 +6,8 @@ encoders_decoders.py:24-257, samplenet_pointnet_ae.py:57-74, 122-149) on HIP ker
 
 The encoder runs on the kernels of the sampler's own feature extractor (pointnet.py: the one-call conv stack in training mode where
 the shape allows, sn_layer_forward_bn otherwise; sn_linear_forward + sn_bn_eval_coef in eval mode); unlike the sampler's extractor
-it hands a gradient to its INPUT -- the sampler is trained through the frozen autoencoder.  Forward and backward are pointnet.py's
-layer-by-layer walk (_conv_stack_fwd, _pool_bwd_bn, _conv_stack_bwd: data gradient only when frozen).  The decoder runs as the sn_skinny_linear
+it hands a gradient to its INPUT -- the sampler is trained through the frozen autoencoder.  Forward and backward are stack_node.py's
+node around pointnet.py's layer-by-layer walk (data gradient only when frozen).  The decoder runs as the sn_skinny_linear
 composition (three launches each way, row blocks of 128); weight gradients of a trainable decoder come from sn_skinny_wgrad.  A
 single-launch decoder was built, lost to the composition and is NOT part of the library (profiles/ae/
 decoder_single_launch_experiment.txt).  There is no CPU route.
@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import pointnet
+from . import pointnet, stack_node
 from ._lib import stream_of
 from .task_features import _skinny, _skinny_wgrad, _trunk_scratch
 
@@ -29,49 +29,6 @@ CONV_STACK = True  # test hook: False = the encoder's training forward layer by 
 
 def _conv_layers(net):
     return [pointnet._Layer("conv%d" % i, getattr(net, "conv%d" % i), "bn%d" % i, getattr(net, "bn%d" % i)) for i in range(1, 6)]
-
-
-class _EncoderFunction(torch.autograd.Function):
-    """x (B, N, 3) -> pooled features (B, bottleneck); differentiable w.r.t. x and, for a trainable network, the 20 parameters."""
-
-    @staticmethod
-    def forward(ctx, net, training, x, *params):
-        convs = _conv_layers(net)
-        B, N, _ = x.shape
-        C5 = convs[-1].Co
-        with torch.cuda.device(x.device):
-            pooled, argsel, zsel = pointnet._pool_bufs(B, C5, x)
-            saved = {"x": x, "B": B, "N": N, "pooled": pooled, "argsel": argsel, "zsel": zsel}
-            fuse = (training and CONV_STACK and B * N > 64 and N % 64 == 0 and C5 % 64 == 0 and convs[-1].Ci % 64 == 0
-                    and pointnet._conv_stack_fx(net, convs, x, B, N, saved, pooled, argsel, zsel))
-            if not fuse:
-                saved["zc"], saved["cc"] = pointnet._conv_stack_fwd(convs, x, training, (pooled, argsel, zsel))
-            elif any(ctx.needs_input_grad):
-                # the per-layer backward reads the xyz layer's output, which the one-call stack may not have kept: rebuilt here,
-                # in the forward, so that a differentiated step issues its launches in one fixed order (nothing when no gradient is asked)
-                pointnet._z1(convs, saved)
-        ctx.net, ctx.training, ctx.saved = net, bool(training), saved
-        return pooled
-
-    @staticmethod
-    def backward(ctx, g):
-        net, saved = ctx.net, ctx.saved
-        convs = _conv_layers(net)
-        fixed = not ctx.training
-        trainable = any(ctx.needs_input_grad[3:])
-        g = g.contiguous().float()
-        grads = {}
-        with torch.cuda.device(g.device):
-            gsel, kcoef = pointnet._pool_bwd_bn(convs[-1], saved, g, fixed, None, grads)
-            gx = pointnet._conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, wgrads=trainable, input_grad=ctx.needs_input_grad[2])
-        out = [None] * len(_ENC_PARAMS)
-        if trainable:
-            out = [grads[n] if ctx.needs_input_grad[3 + j] else None for j, n in enumerate(_ENC_PARAMS)]
-        return (None, None, None if gx is None else gx.view(saved["x"].shape)) + tuple(out)
-
-
-_ENC_PARAMS = tuple("conv%d.%s" % (i, k) for i in range(1, 6) for k in ("weight", "bias")) + \
-    tuple("bn%d.%s" % (i, k) for i in range(1, 6) for k in ("weight", "bias"))
 
 
 class _DecoderFunction(torch.autograd.Function):
@@ -175,8 +132,10 @@ class PointNetAE(nn.Module):
             x = x.permute(0, 2, 1)
         if x.dim() != 3 or x.shape[2] != 3:
             raise RuntimeError("shape of x must be of [Batch x NumInPoints x 3] ('bnc') or [Batch x 3 x NumInPoints] ('bcn')")
-        params = [self.get_parameter(n) for n in _ENC_PARAMS]
-        return _EncoderFunction.apply(self, self.training, x.contiguous().float(), *params)
+        # eval mode with trainable parameters is allowed here: gradients on fixed statistics
+        spec = stack_node.StackSpec(_conv_layers(self), self.training, stack_node.POOL_POINTS, self if CONV_STACK else None,
+                                    stack_node.WGRADS_ASKED, None)
+        return stack_node.conv_stack(spec, x.contiguous().float())[0]
 
     def decode(self, z):
         """z (B, bottleneck) -> (B, n_pc_points, 3): row-major reshape of the last layer's 3 * n_pc_points columns

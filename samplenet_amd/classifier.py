@@ -7,8 +7,8 @@ pointnet_cls_basic.py:55-136) on HIP kernels.
                points -> fc1 512 -> dropout -> fc2 256 -> dropout -> fc3 num_classes       (every conv / hidden fc: bn + relu)
     PointNetClsBasic  the same without the two T-Nets and with dropout behind fc2 only
 
-Every conv stack runs on pointnet.py's layer-by-layer walk (_conv_stack_fwd, _pool_bwd_bn, _conv_stack_bwd: the GEMM entries of the
-sampler's own head; data gradient only when the network is frozen).  The three FC heads (1024 -> 512 -> 256 -> 9 / 4096 / classes)
+Every conv stack runs on stack_node.py's node around pointnet.py's layer-by-layer walk (the GEMM entries of the sampler's own head;
+data gradient only when the network is frozen).  The three FC heads (1024 -> 512 -> 256 -> 9 / 4096 / classes)
 of a frozen network on running statistics -- the sampler-training configuration -- run as the sn_skinny_linear composition
 (_SkinnyHeadFunction); on batch statistics or with trainable weights they are the N = 1 case of the same walk.  What the library had no kernel for are the
 per-cloud transforms (sn_cloud_transform_*), the orthogonality regulariser (sn_orthogonality_loss_*) and the activated output of a
@@ -26,95 +26,24 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import pointnet
+from . import pointnet, stack_node
 from ._lib import check, lib, ptr, stream_of
 
 
-_EVAL_WGRAD = ("samplenet_amd.classifier: weight gradients need training mode (.train()); an eval-mode network is differentiated "
-               "w.r.t. its input only -- freeze it with requires_grad_(False)")
+_WGRAD_NEEDS_TRAINING = stack_node.eval_wgrad_error("classifier", "network")
 
 
 def _layer(mod, conv, bn, prefix=""):
     return pointnet._Layer(prefix + conv, getattr(mod, conv), prefix + bn, getattr(mod, bn))
 
 
-def _params(layers):
-    out = []
-    for L in layers:
-        out += [L.W, L.b]
-    for L in layers:
-        out += [L.bn.weight, L.bn.bias]
-    return out
-
-
-def _param_names(layers):
-    return [L.name + k for L in layers for k in (".weight", ".bias")] + [L.bn_name + k for L in layers for k in (".weight", ".bias")]
-
-
-class _StackFunction(torch.autograd.Function):
-    """relu(bn(conv1d_k1(.))) x len(layers) on x (B, N, Ci) -> the max over the points (B, Co) when pool, else the activated
-    features (B, N, Co).  Differentiable w.r.t. x and, in training mode, the layers' parameters.  An FC head is the N = 1 case."""
-
-    @staticmethod
-    def forward(ctx, layers, pool, training, x, *params):
-        B, N, _ = x.shape
-        Co = layers[-1].Co
-        with torch.cuda.device(x.device):
-            saved = {"x": x, "B": B, "N": N}
-            if pool:
-                pooled, argsel, zsel = pointnet._pool_bufs(B, Co, x)
-                saved.update(pooled=pooled, argsel=argsel, zsel=zsel)
-                saved["zc"], saved["cc"] = pointnet._conv_stack_fwd(layers, x, training, (pooled, argsel, zsel))
-                out = pooled
-            else:
-                saved["zc"], saved["cc"] = pointnet._conv_stack_fwd(layers, x, training, None)
-                out = torch.empty(B, N, Co, device=x.device, dtype=torch.float32)
-                check(lib.sn_bn_relu_forward(B * N, Co, ptr(saved["zc"][-1]), ptr(saved["cc"][-1]), ptr(out), stream_of(x)),
-                      "sn_bn_relu_forward")
-        ctx.layers, ctx.pool, ctx.training, ctx.saved = layers, pool, bool(training), saved
-        if pool:
-            ctx.mark_non_differentiable(argsel)
-            return out, argsel
-        return out
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        layers, saved = ctx.layers, ctx.saved
-        fixed = not ctx.training
-        trainable = any(ctx.needs_input_grad[4:])
-        if trainable and fixed:
-            raise RuntimeError(_EVAL_WGRAD)
-        g = g.contiguous().float()
-        top = layers[-1]
-        R = saved["B"] * saved["N"]
-        grads = {}
-        with torch.cuda.device(g.device):
-            if ctx.pool:
-                gsel, kcoef = pointnet._pool_bwd_bn(top, saved, g, fixed, None, grads)
-                dy = None
-            else:
-                gsel = None
-                z, coef = saved["zc"][-1], saved["cc"][-1]
-                dy = torch.empty(R, top.Co, device=g.device, dtype=torch.float32)
-                check(lib.sn_bn_relu_backward(R, top.Co, ptr(z), ptr(coef), ptr(g), 0, ptr(dy), stream_of(g)), "sn_bn_relu_backward")
-                if fixed:
-                    kcoef = torch.zeros(3, top.Co, device=g.device, dtype=torch.float32)
-                    kcoef[0].copy_(coef[0])
-                else:
-                    # (sum dY, sum dY Z) of the top BatchNorm as ONE block of partials; training mode need not be fast
-                    stats = torch.stack((dy.sum(0), (dy * z).sum(0))).view(1, 2, top.Co).contiguous()
-                    dgam, dbet, dbias, kcoef = pointnet._bn_bwd(top, R, stats, 1, coef)
-                    grads[top.bn_name + ".weight"], grads[top.bn_name + ".bias"], grads[top.name + ".bias"] = dgam, dbet, dbias
-            gx = pointnet._conv_stack_bwd(layers, saved, gsel, kcoef, fixed, grads, wgrads=trainable,
-                                          input_grad=ctx.needs_input_grad[3], dy_top=dy)
-        out = [None] * (4 * len(layers))
-        if trainable:
-            out = [grads[n] if ctx.needs_input_grad[4 + j] else None for j, n in enumerate(_param_names(layers))]
-        return (None, None, None, None if gx is None else gx.view(saved["x"].shape)) + tuple(out)
-
-
 def _stack(layers, pool, training, x):
-    return _StackFunction.apply(layers, pool, training, x.contiguous().float(), *_params(layers))
+    """relu(bn(conv1d_k1(.))) x len(layers) on x (B, N, Ci) -> (the max over the points (B, Co), argsel) when pool, else the activated
+    features (B, N, Co).  Differentiable w.r.t. x and, in training mode, the layers' parameters.  An FC head is the N = 1 case."""
+    spec = stack_node.StackSpec(layers, bool(training), stack_node.POOL_POINTS if pool else stack_node.POOL_NONE, None,
+                                stack_node.WGRADS_ASKED, _WGRAD_NEEDS_TRAINING)
+    out, argsel = stack_node.conv_stack(spec, x.contiguous().float())
+    return (out, argsel) if pool else out
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -135,7 +64,7 @@ class _LinearFunction(torch.autograd.Function):
         R = x.shape[0]
         gx = dW = db = None
         if (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) and not ctx.training:
-            raise RuntimeError(_EVAL_WGRAD)
+            raise RuntimeError(_WGRAD_NEEDS_TRAINING)
         with torch.cuda.device(g.device):
             if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
                 dW, db = pointnet._wgrad(R, L, pointnet.DZ_PLAIN, g, None, None, None, None, 1, x, None, True)
@@ -144,18 +73,8 @@ class _LinearFunction(torch.autograd.Function):
         return None, None, gx, dW, db
 
 
-class _Plain:
-    """_Layer record of a Linear without BatchNorm."""
-
-    __slots__ = ("name", "W", "b", "Ci", "Co")
-
-    def __init__(self, name, lin):
-        self.name, self.W, self.b = name, lin.weight, lin.bias
-        self.Co, self.Ci = lin.weight.shape
-
-
 def _linear(name, lin, training, x):
-    return _LinearFunction.apply(_Plain(name, lin), training, x, lin.weight, lin.bias)
+    return _LinearFunction.apply(pointnet._Layer(name, lin, None, None), training, x, lin.weight, lin.bias)
 
 
 SKINNY_HEADS = True  # test hook: False = a frozen eval-mode FC head on the layer walk (sn_linear_forward / sn_linear_dgrad) as well
@@ -229,8 +148,8 @@ class _SkinnyHeadFunction(torch.autograd.Function):
 def _head(hidden, lin_name, lin, training, x):
     """relu(bn(fc)) x len(hidden) -> linear on x (B, C0) -> (output, last hidden activation): the sn_skinny_linear composition for
     a frozen network on running statistics, pointnet.py's layer walk otherwise (batch statistics, weight gradients)."""
-    last = _Plain(lin_name, lin)
-    frozen = not any(p.requires_grad for p in _params(hidden) + [lin.weight, lin.bias])
+    last = pointnet._Layer(lin_name, lin, None, None)
+    frozen = not any(p.requires_grad for p in pointnet.stack_params(hidden) + [lin.weight, lin.bias])
     if SKINNY_HEADS and not training and frozen:
         rows = min(x.shape[0], 128)
         if all(lib.sn_skinny_linear_supported(rows, L.Ci, L.Co) and lib.sn_skinny_linear_supported(rows, L.Co, L.Ci) for L in hidden + [last]):

@@ -7,7 +7,7 @@ while the parameters stay ordinary nn.Conv1d / nn.BatchNorm1d / nn.Linear member
 (state_dict compatibility).  Host side: buffer allocation and launch sequencing only.
 
 The layer-by-layer walk of a conv stack (_conv_stack_fwd / _pool_bwd_bn / _conv_stack_bwd) lives here once: this head, the
-synchronised-statistics mode (syncbn.py) and the autoencoder's encoder (autoencoder.py) all drive it.
+synchronised-statistics mode (syncbn.py) and the task networks' node (stack_node.py) all drive it.
 """
 import ctypes
 
@@ -75,18 +75,7 @@ def _layers(net):
     nfc = getattr(net, "num_fc_layers", 4)
     fcs = [_Layer("fc%d" % i, getattr(net, "fc%d" % i), "bn_fc%d" % i, getattr(net, "bn_fc%d" % i, None) if i < nfc else None)
            for i in range(1, nfc + 1)]
-    names = []
-    for L in convs + fcs:
-        names += [L.name + ".weight", L.name + ".bias"]
-    for L in convs + fcs:
-        if L.bn is not None:
-            names += [L.bn_name + ".weight", L.bn_name + ".bias"]
-    params = []
-    for L in convs + fcs:
-        params += [L.W, L.b]
-    for L in convs + fcs:
-        if L.bn is not None:
-            params += [L.bn.weight, L.bn.bias]
+    names, params = stack_param_names(convs + fcs), stack_params(convs + fcs)
     ob = None
     if out_bn is not None:  # the BatchNorm behind the last FC layer: differentiated by the node as well (out_bn below)
         ob = ("bn_fc%d" % nfc, out_bn)
@@ -94,6 +83,19 @@ def _layers(net):
         params += [out_bn.weight, out_bn.bias]
     d["_sn_layer_records"] = (convs, fcs, tuple(names), tuple(params), ob)
     return convs, fcs
+
+
+def stack_params(layers):
+    """The parameters of a run of _Layer records in the order every node takes them and returns their gradients: W, b per layer (b
+    skipped where the layer has none), then bn.weight, bn.bias per layer with a BatchNorm."""
+    return [p for L in layers for p in (L.W, L.b) if p is not None] + \
+        [p for L in layers if L.bn is not None for p in (L.bn.weight, L.bn.bias)]
+
+
+def stack_param_names(layers):
+    """The state-dict names of stack_params(layers), in its order."""
+    return [L.name + k for L in layers for k, p in ((".weight", L.W), (".bias", L.b)) if p is not None] + \
+        [L.bn_name + k for L in layers if L.bn is not None for k in (".weight", ".bias")]
 
 
 def _plain_out_bn(net, mods):
@@ -744,6 +746,13 @@ def _bn_bwd(L, R, stats, nblk, coef, sink=None, bn_name="", lin_name=""):
     return dgamma, dbeta, dbias, kcoef
 
 
+def _fixed_kcoef(coef):
+    """The dZ coefficients of a BatchNorm on running statistics out of its forward block `coef`: dZ = scale * dY, nothing else."""
+    kcoef = torch.zeros(3, coef.shape[1], device=coef.device, dtype=torch.float32)
+    kcoef[0].copy_(coef[0])
+    return kcoef
+
+
 def _layer_bwd(R, L, mode, dy, z, kcoef, gsel, argsel, npts, zprev, coef_prev, Lprev, sink, name, bn_prev, lin_prev,
                with_bias, prev_bn_rows=0):
     """Backward of layer `name`: dW (db when with_bias), dYprev and -- when the layer below (Lprev) has a BatchNorm --
@@ -847,8 +856,7 @@ def _conv_stack_bwd(convs, saved, gsel, kcoef, fixed, grads, sink=None, wgrads=T
         else:
             dy, stats, nblk = _dgrad(R, L, mode, dy, zc[i], kcoef, gs, ag, N, zprev, cc[i - 1])
             if fixed:
-                kcoef = torch.zeros(3, Lp.Co, device=dy.device, dtype=torch.float32)
-                kcoef[0].copy_(cc[i - 1][0])
+                kcoef = _fixed_kcoef(cc[i - 1])
             else:
                 kcoef = _bn_bwd(Lp, R, stats, nblk, cc[i - 1])[3]
     L1 = convs[0]

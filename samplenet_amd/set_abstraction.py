@@ -3,7 +3,7 @@
     grouped rows (G, S, Ci), channels contiguous  ->  relu(bn(conv_1x1(.))) x L  ->  max over the S rows of a group  ->  (G, Co)
 
 with G = B * npoint groups of S = nsample rows (ops.ball_group_rows writes them in this layout), or G = B, S = N for a group-all level.
-The layers run on pointnet.py's layer-by-layer walk (_conv_stack_fwd, _conv_stack_bwd: the GEMM entries with fused BatchNorm of the
+The layers run on stack_node.py's node around pointnet.py's layer-by-layer walk (the GEMM entries with fused BatchNorm of the
 sampler's own head), differentiable towards the rows (input_grad=True) and, in training mode, the parameters.  The pool is one of two
 pairs, picked by group_pool_route(G, S): sn_group_pool_forward / sn_group_pool_backward + sn_bn_backward_coef (a wave per group and
 64 channels: many small groups), or sn_pool_forward / sn_pool_backward_bn (a workgroup per group: few large groups).  The forward
@@ -14,13 +14,9 @@ the memory of (Co, Ci).  With a BatchNorm the conv has no bias: the GEMMs get NU
 dZ, which the kernels write in any case) land in scratch tensors handed over as its sink.
 BatchNorm follows torch: .train() = batch statistics and a running-statistics update, .eval() = running statistics; weight gradients
 need training mode.  No float atomics anywhere on this route.  Capturing the node's backward in a graph is not supported."""
-import torch
+from . import pointnet, stack_node
 
-from . import pointnet
-from ._lib import check, lib, ptr, stream_of
-
-_EVAL_WGRAD = ("samplenet_amd.set_abstraction: weight gradients need training mode (.train()); an eval-mode module is differentiated "
-               "w.r.t. its input only -- freeze it with requires_grad_(False)")
+_WGRAD_NEEDS_TRAINING = stack_node.eval_wgrad_error("set_abstraction", "module")
 
 # Test hook: None = group_pool_route's rule, True / False = that pair wherever it is legal.
 FORCE_GROUP_POOL = None
@@ -49,68 +45,6 @@ def fused_supported(mlp):
     return len(mlp) >= 2 and all(getattr(m, "bn", None) is not None for m in mlp)
 
 
-def _params(layers):
-    return [L.W for L in layers] + [p for L in layers for p in (L.bn.weight, L.bn.bias)]
-
-
-def _param_names(layers):
-    return [L.name + ".weight" for L in layers] + [L.bn_name + k for L in layers for k in (".weight", ".bias")]
-
-
-class _SetAbstractionFunction(torch.autograd.Function):
-    """rows (G, S, Ci) -> pooled (G, Co), argsel (G, Co) int32: the shared MLP and the max over every group's rows."""
-
-    @staticmethod
-    def forward(ctx, layers, training, group_pool, rows, *params):
-        G, S, _ = rows.shape
-        Co = layers[-1].Co
-        with torch.cuda.device(rows.device):
-            pooled, argsel, zsel = pointnet._pool_bufs(G, Co, rows)
-            zc, cc = pointnet._conv_stack_fwd(layers, rows, training, None)
-            fn, name = (lib.sn_group_pool_forward, "sn_group_pool_forward") if group_pool else (lib.sn_pool_forward, "sn_pool_forward")
-            check(fn(G, S, Co, ptr(zc[-1]), ptr(cc[-1]), ptr(pooled), ptr(argsel), ptr(zsel), stream_of(rows)), name)
-        ctx.layers, ctx.training, ctx.group_pool = layers, bool(training), bool(group_pool)
-        ctx.saved = {"x": rows, "B": G, "N": S, "zc": zc, "cc": cc, "pooled": pooled, "argsel": argsel, "zsel": zsel}
-        ctx.mark_non_differentiable(argsel)
-        return pooled, argsel
-
-    @staticmethod
-    def backward(ctx, g, _ga):
-        layers, saved = ctx.layers, ctx.saved
-        fixed = not ctx.training
-        trainable = any(ctx.needs_input_grad[4:])
-        if trainable and fixed:
-            raise RuntimeError(_EVAL_WGRAD)
-        g = g.contiguous().float()
-        top = layers[-1]
-        G, S, C = saved["B"], saved["N"], top.Co
-        grads = {}
-        with torch.cuda.device(g.device):
-            # the convs have no bias: the kernels' bias-gradient outputs go to scratch
-            sink = {L.name + ".bias": torch.empty(L.Co, device=g.device, dtype=torch.float32) for L in layers}
-            if ctx.group_pool:
-                coef = saved["cc"][-1]
-                gsel = torch.empty(G, C, device=g.device, dtype=torch.float32)
-                nblk = lib.sn_group_pool_stats_blocks(G)
-                stats = None if fixed else torch.empty(nblk, 2, C, device=g.device, dtype=torch.float32)
-                check(lib.sn_group_pool_backward(G, C, ptr(g), ptr(saved["pooled"]), ptr(saved["zsel"]), ptr(gsel), ptr(stats),
-                                                 stream_of(g)), "sn_group_pool_backward")
-                if fixed:
-                    kcoef = torch.zeros(3, C, device=g.device, dtype=torch.float32)
-                    kcoef[0].copy_(coef[0])
-                else:
-                    dgam, dbet, _, kcoef = pointnet._bn_bwd(top, G * S, stats, nblk, coef, sink, top.bn_name, top.name)
-                    grads[top.bn_name + ".weight"], grads[top.bn_name + ".bias"] = dgam, dbet
-            else:
-                gsel, kcoef = pointnet._pool_bwd_bn(top, saved, g, fixed, sink, grads)
-            gx = pointnet._conv_stack_bwd(layers, saved, gsel, kcoef, fixed, grads, sink=sink, wgrads=not fixed,
-                                          input_grad=ctx.needs_input_grad[3])
-        out = [None] * (3 * len(layers))
-        if trainable:
-            out = [grads[n] if ctx.needs_input_grad[4 + j] else None for j, n in enumerate(_param_names(layers))]
-        return (None, None, None, None if gx is None else gx.view(saved["x"].shape)) + tuple(out)
-
-
 def grouped_mlp_max(mlp, rows, return_argsel=False):
     """rows (G, S, Ci) float32 on the GPU, mlp a shared_mlp Sequential (fused_supported) -> (G, mlp[-1] width): relu(bn(conv)) per
     layer on every row, then the max over each group's S rows.  mlp.training selects batch or running statistics."""
@@ -122,5 +56,8 @@ def grouped_mlp_max(mlp, rows, return_argsel=False):
     if rows.dim() != 3 or rows.shape[2] != layers[0].Ci or rows.shape[0] * rows.shape[1] == 0:
         raise ValueError("set_abstraction: rows must be (G, S, %d) with G, S >= 1, got %s" % (layers[0].Ci, tuple(rows.shape)))
     G, S, _ = rows.shape
-    pooled, argsel = _SetAbstractionFunction.apply(layers, mlp.training, group_pool_route(G, S), rows.contiguous().float(), *_params(layers))
+    # (walks with weight gradients whenever the module is in training mode, frozen or not)
+    spec = stack_node.StackSpec(layers, mlp.training, stack_node.POOL_GROUPS if group_pool_route(G, S) else stack_node.POOL_POINTS, None,
+                                stack_node.WGRADS_TRAINING, _WGRAD_NEEDS_TRAINING)
+    pooled, argsel = stack_node.conv_stack(spec, rows.contiguous().float())
     return (pooled, argsel) if return_argsel else pooled

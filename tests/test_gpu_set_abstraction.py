@@ -1,11 +1,15 @@
 """The set-abstraction modules of the pointnet2 stand-in (PointnetSAModule, PointnetSAModuleMSG) on the GPU, B = 2, train and eval.
 
-Bit for bit: the fused forward against the composition of this library's existing launches -- ops.ball_group, a permute,
-classifier._StackFunction with pool=True (the same GEMM launches on the same data; the pool is a pure selection) --, the running
+Bit for bit: the fused forward against the composition of this library's existing launches -- ops.ball_group, a permute, the
+conv-stack node (stack_node.py) with the points pool and zero bias tensors, as the classifier runs a pooled stack (the same GEMM
+launches on the same data; the pool is a pure selection) --, the running
 statistics and num_batches_tracked after a training step against that composition's, and the weight / BatchNorm gradients wherever
 the existing pool pair is the chosen route (at these sizes set_abstraction.group_pool_route always chooses it; every case runs a
 second time with the group-pool pair forced, where the forward must still agree bit for bit and the gradients are held to float64).
 Two runs of forward + backward give identical bits for every gradient: no float atomics on the fused route.
+Both sides of that comparison are the one node now (once classifier._StackFunction against a node of set abstraction's own), so it no
+longer anchors the MLP half; what it still separates: the grouping route (ops.ball_group + permute against the row-layout launch), the
+bias route (a zero bias tensor against NULL + sink) and the pool pair.  The MLP half's anchor is the float64 comparison below.
 
 Against float64: a hand-written float64 run of the composition a user would write (grouping, 1 x 1 convolutions, BatchNorm, ReLU, max)
 on the kernel's own idx, its pool teacher-forced with the GPU's argsel -- after every GPU pick was verified to reach the float64
@@ -111,8 +115,8 @@ def run(m, level, fused, seed=0):
 
 
 class _ZeroBiasLayer:
-    """pointnet._Layer record of a bias-free conv for classifier._StackFunction, whose backward allocates the bias gradient like the
-    bias: a zero bias tensor (z + 0 has z's bits)."""
+    """pointnet._Layer record of a bias-free conv on the bias route: a zero bias tensor (z + 0 has z's bits), whose gradient the
+    backward allocates like the bias instead of sending it to the sink."""
 
     def __init__(self, name, conv, bn_name, bn):
         self.name, self.bn_name, self.W, self.bn = name, bn_name, conv.weight, bn
@@ -139,7 +143,7 @@ def composition(m, level, seed=0):
             g = ops.ball_group(cfg["radii"][i], cfg["nsamples"][i], xyz, new_xyz, f, use_xyz=True, rule="squared")
             x = g.permute(0, 2, 3, 1).contiguous().view(B * cfg["npoint"], cfg["nsamples"][i], g.shape[1])
         layers = [_ZeroBiasLayer("%d.conv" % j, l.conv, "%d.bn" % j, l.bn) for j, l in enumerate(mlp)]
-        pooled, _ = classifier._StackFunction.apply(layers, True, training, x, *classifier._params(layers))
+        pooled, _ = classifier._stack(layers, True, training, x)   # the node with the points pool; x is float32 contiguous already
         outs.append(pooled.view(B, -1, pooled.shape[1]))
     out = torch.cat(outs, dim=2).transpose(1, 2).contiguous()
     got = {"out": out.detach()}
@@ -311,3 +315,19 @@ def test_fused_false_and_unsupported_specs_take_the_torch_route():
     m = PM.PointnetSAModule([4, 16, 16], npoint=6, radius=0.5, nsample=4).cuda().eval()
     with pytest.raises(RuntimeError):
         m(xyz, f)[1].sum().backward()
+
+
+def test_grouped_mlp_max_refuses_weight_gradients_in_eval_mode():
+    from samplenet_amd import set_abstraction
+    from samplenet_amd.compat.pointnet2.utils import pointnet2_modules as PM
+
+    torch.manual_seed(0)
+    mlp = PM.PointnetSAModule([5, 16, 16], npoint=2, radius=0.5, nsample=4, use_xyz=False).cuda().eval().mlps[0]
+    assert mlp[0].conv.in_channels == 5 and all(p.requires_grad for p in mlp.parameters())
+    rows = torch.randn(2, 4, 5, device="cuda", requires_grad=True)
+    out = set_abstraction.grouped_mlp_max(mlp, rows)
+    assert out.shape == (2, 16)
+    with pytest.raises(RuntimeError) as e:
+        out.sum().backward()
+    assert str(e.value) == ("samplenet_amd.set_abstraction: weight gradients need training mode (.train()); an eval-mode module is "
+                            "differentiated w.r.t. its input only -- freeze it with requires_grad_(False)")
