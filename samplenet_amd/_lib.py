@@ -16,7 +16,7 @@ import torch  # noqa: F401  -- first: its bundled HIP runtime (libamdhip64.so.7)
 # because the streams and device pointers handed to the library come from torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SAMPLENET_AMD_LIB: another build of the SAME library (same ABI; tools/build_variant.sh -- same-box A/B of a kernel change)
+# SAMPLENET_AMD_LIB: another build of the SAME library (same ABI; build.py --variant / --timeline -- same-box A/B of a kernel change)
 LIB_PATH = os.environ.get("SAMPLENET_AMD_LIB") or os.path.join(_HERE, "lib", "libsamplenet_hip.so")
 # include/samplenet_hip.h: the drop-in boundary; include/samplenet_hip_internal.h: the fused-step entry points behind it
 HEADERS = [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("samplenet_hip.h", "samplenet_hip_internal.h")]

@@ -3,7 +3,7 @@
 // launch per direction; task_network.hip: the task network's BatchNorm-free extractor and skinny trunk): operand loaders, the fp32 and split-bf16 GEMM tile cores,
 // fixed-point BatchNorm statistics, BatchNorm finalisation / backward expressions, pool keys, LDS-only barrier and the
 // cross-wave reduce-scatter.  Everything here is inline device code or a template: each translation unit instantiates what it
-// launches.  Debug builds (-DSN_TIMELINE: tools/build_timeline_lib.sh compiles the four units as ONE so that the stamp buffers
+// launches.  Debug builds (-DSN_TIMELINE: build.py --timeline compiles the four units as ONE so that the stamp buffers
 // exist once) also carry the phase-stamp buffers and their read-out entries.
 #pragma once
 #include <algorithm>

@@ -2,7 +2,6 @@
 include/samplenet_hip.h declares; the ctypes prototype table covers the header; host-side utilities behave like the
 reference's (sputils); the product refuses to run without a GPU instead of falling back."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -10,18 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from built_lib import ensure_built, load_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def libpath():
-    path = os.path.join(ROOT, "samplenet_amd", "lib", "libsamplenet_hip.so")
-    if not os.path.exists(path):  # hipcc cross-compiles gfx950 without a GPU
-        spec = importlib.util.spec_from_file_location("sn_build", os.path.join(ROOT, "samplenet_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    return path
+    return ensure_built()
 
 
 def _header_functions(which=("samplenet_hip.h", "samplenet_hip_internal.h")):
@@ -280,6 +275,23 @@ def test_bench_self_launches_its_ranks(tmp_path):
         assert r.returncode == 2 and "exposes 0 GPU" in r.stderr and "Traceback" not in r.stderr
 
 
+def _device_disassembly(obj, tmp_path):
+    """llvm-objdump -d of the gfx950 code object bundled in a hipcc object file; None where it carries no device code."""
+    import subprocess
+
+    llvm = "/opt/rocm/lib/llvm/bin"
+    fat = str(tmp_path / (os.path.basename(obj) + ".fat"))
+    r = subprocess.run([llvm + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, obj], capture_output=True, text=True)
+    if r.returncode != 0 or not os.path.exists(fat):
+        return None
+    lst = subprocess.run([llvm + "/clang-offload-bundler", "--list", "--type=o", "--input=" + fat], capture_output=True, text=True).stdout
+    tgt = [t for t in lst.split() if "gfx950" in t]
+    assert tgt, (obj, lst)
+    co = fat[:-4] + ".co"
+    subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + tgt[0], "--input=" + fat, "--output=" + co])
+    return subprocess.run([llvm + "/llvm-objdump", "-d", co], capture_output=True, text=True).stdout
+
+
 def test_device_code_carries_no_packed_fp32_arithmetic(tmp_path):
     """The product build switches the packed fp32 VALU ops off (samplenet_amd/build.py NO_PACKED_F32): with a second process on the
     GPU, kernels carrying the compiler's SLP-packed v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 returned wrong low halves in ~1 % of
@@ -289,25 +301,15 @@ def test_device_code_carries_no_packed_fp32_arithmetic(tmp_path):
     register pair disjoint from every source pair (the aliasing is the stated trigger: an instruction whose sources survive it
     gives the same result however often a restored wave replays it), and it must hold a sensible number of them (the EMD sweeps
     are built on them: a lost feature flag shows up here too)."""
-    import subprocess
-
-    llvm = "/opt/rocm/lib/llvm/bin"
     libdir = os.path.join(ROOT, "samplenet_amd", "lib")
     objs = sorted(f for f in os.listdir(libdir) if f.endswith(".o"))
     assert len(objs) >= 8
     checked = 0
     for o in objs:
-        fat = str(tmp_path / (o + ".fat"))
-        r = subprocess.run([llvm + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, os.path.join(libdir, o)], capture_output=True, text=True)
-        if r.returncode != 0 or not os.path.exists(fat):
+        dis = _device_disassembly(os.path.join(libdir, o), tmp_path)
+        if dis is None:
             continue  # (capi_common: host code only)
-        lst = subprocess.run([llvm + "/clang-offload-bundler", "--list", "--type=o", "--input=" + fat], capture_output=True, text=True).stdout
-        tgt = [t for t in lst.split() if "gfx950" in t]
-        assert tgt, (o, lst)
-        co = str(tmp_path / (o + ".co"))
-        subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + tgt[0], "--input=" + fat, "--output=" + co])
-        dis = subprocess.run([llvm + "/llvm-objdump", "-d", co], capture_output=True, text=True).stdout
-        pk = re.findall(r"\bv_pk_(?:fma|mul|add)_f32\s+([^\n]*)", dis)
+        pk =re.findall(r"\bv_pk_(?:fma|mul|add)_f32\s+([^\n]*)", dis)
         if o == "emd.o":
             assert len(pk) >= 100, "emd.o: the hand-written packed sweeps are gone (%d packed instructions)" % len(pk)
             for ops in pk:
@@ -328,21 +330,13 @@ def test_emd_scalar_build_switch_compiles_without_packed_instructions(tmp_path):
     misbehave under co-tenancy; nothing else would notice if it stopped compiling or kept a packed instruction."""
     import subprocess
 
-    llvm = "/opt/rocm/lib/llvm/bin"
-    src = os.path.join(ROOT, "samplenet_amd", "csrc", "emd.hip")
+    build = load_build()
+    unit, flags = build.EMD_SCALAR
     obj = str(tmp_path / "emd_scalar.o")
-    cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "-c", src, "-o", obj, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "samplenet_amd", "csrc"), "-Wall",
-           "-Wno-unused-function", "-Werror", "-ffp-contract=off", "-fno-slp-vectorize", "-DSN_EMD_SCALAR_F32=1",
-           "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+    cmd = build.compile_command(os.path.join(build.CSRC, unit), obj, extra=flags + ["-Werror"])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
-    fat, co = obj + ".fat", obj + ".co"
-    subprocess.check_call([llvm + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, obj])
-    lst = subprocess.run([llvm + "/clang-offload-bundler", "--list", "--type=o", "--input=" + fat], capture_output=True, text=True).stdout
-    tgt = [t for t in lst.split() if "gfx950" in t]
-    subprocess.check_call([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + tgt[0], "--input=" + fat, "--output=" + co])
-    dis = subprocess.run([llvm + "/llvm-objdump", "-d", co], capture_output=True, text=True).stdout
+    dis = _device_disassembly(obj, tmp_path)
     assert "s_endpgm" in dis and "v_exp_f32" in dis
     assert not re.findall(r"\bv_pk_(?:fma|mul|add)_f32\b", dis)
 
@@ -351,19 +345,22 @@ def test_fp32_mfma_twin_of_the_conv_gemms_still_compiles(tmp_path):
     """pointnet_mlp.hip / pointnet_mlp_backward.hip carry a second implementation of the conv-stack GEMMs and of the fused conv
     backward on the fp32 MFMA (-DSN_BF16X3=0: exact fp32 products instead of six bf16 products of three-way split operands) -- the
     arithmetic reference of the split kernels (tests/test_gpu_mlp.py::test_fp32_mfma_twin_agrees_with_the_split_bf16_build runs it
-    on the GPU).  It is not a product build, so nothing else would notice if it stopped compiling."""
+    on the GPU).  It is not a product build, so nothing else would notice if it stopped compiling -- or if it carried the
+    compiler's packed fp32 arithmetic, which the product's flags keep out (test_device_code_carries_no_packed_fp32_arithmetic only
+    sees the product's objects)."""
     import subprocess
 
+    build = load_build()
     procs = []
     for unit in ("pointnet_mlp", "pointnet_mlp_backward"):
-        src = os.path.join(ROOT, "samplenet_amd", "csrc", unit + ".hip")
-        cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "-c", src, "-o", str(tmp_path / (unit + "0.o")), "-O3", "-std=c++17", "-fPIC",
-               "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "samplenet_amd", "csrc"),
-               "-Wall", "-Wno-unused-function", "-Werror", "-DSN_BF16X3=0"]
-        procs.append((unit, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
-    for unit, p in procs:
+        obj = str(tmp_path / (unit + "0.o"))
+        cmd = build.compile_command(os.path.join(build.CSRC, unit + ".hip"), obj, extra=["-DSN_BF16X3=0", "-Werror"])
+        procs.append((unit, obj, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
+    for unit, obj, p in procs:
         _, err = p.communicate(timeout=900)
         assert p.returncode == 0, unit + ": " + err[-3000:]
+        dis = _device_disassembly(obj, tmp_path)
+        assert "s_endpgm" in dis and not re.findall(r"\bv_pk_(?:fma|mul|add)_f32\b", dis), unit
 
 
 def test_bench_profile_provenance_helpers():

@@ -2,7 +2,6 @@
 PyTorch fp32 modules of the same network (the reference's own op chain, samplenet.py:90-104) on the same
 weights and inputs: outputs, BatchNorm running statistics, and the gradient of every parameter."""
 import copy
-import os
 
 import numpy as np
 import pytest
@@ -1115,26 +1114,13 @@ def test_fp32_mfma_twin_agrees_with_the_split_bf16_build(tmp_path):
     forward and its fused backward at R = 4096 -- outputs within 1e-6 of the largest value, i.e. the split products are
     fp32-accurate against the hardware's own fp32 matrix path."""
     import ctypes
-    import subprocess
 
     from samplenet_amd._lib import LIB_PATH, bind
-    from samplenet_amd.build import SOURCES
+    from samplenet_amd.build import build_variant
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    remade = ("pointnet_mlp", "pointnet_mlp_backward")
-    # every other unit of the product build, by the build's own list
-    objs = [os.path.join(root, "samplenet_amd", "lib", n + ".o") for n in (os.path.splitext(src)[0] for src, _ in SOURCES) if n not in remade]
-    if not all(os.path.exists(o) for o in objs):
-        pytest.skip("object files of the product build are not in the tree")
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(root, "include"),
-             "-I" + os.path.join(root, "samplenet_amd", "csrc"), "-Wno-unused-function"]
-    twins = []
-    for unit in remade:
-        twins.append(str(tmp_path / (unit + "0.o")))
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "-c", os.path.join(root, "samplenet_amd", "csrc", unit + ".hip"),
-                               "-o", twins[-1], "-DSN_BF16X3=0"] + flags, timeout=900)
-    so = str(tmp_path / "libsamplenet_hip_fp32.so")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", so] + twins + objs, timeout=600)
+    # the twin units with the product's flags (no compiler-packed fp32 arithmetic: this test runs on a GPU that others share), every
+    # other unit as the product build has it
+    so = build_variant("fp32", {"pointnet_mlp.hip": ["-DSN_BF16X3=0"], "pointnet_mlp_backward.hip": ["-DSN_BF16X3=0"]}, out_dir=str(tmp_path))
     libs = [bind(ctypes.CDLL(path), ("sn_linear_forward", "sn_conv_backward_partials", "sn_linear_wgrad_splits", "sn_linear_stats_blocks"))
             for path in (LIB_PATH, so)]
     g = torch.Generator(device="cuda").manual_seed(2)

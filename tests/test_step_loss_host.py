@@ -17,13 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
-    import importlib.util
+    from built_lib import ensure_built
 
-    if not os.path.exists(os.path.join(ROOT, "samplenet_amd", "lib", "libsamplenet_hip.so")):  # hipcc cross-compiles gfx950 without a GPU
-        spec = importlib.util.spec_from_file_location("sn_build", os.path.join(ROOT, "samplenet_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
+    ensure_built()
     from samplenet_amd._lib import lib as L
 
     return L

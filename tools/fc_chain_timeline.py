@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Phase timeline of the two FC chain kernels inside the captured step (debug build: tools/build_variant.sh tl fc_chain.hip
--DSN_TIMELINE; run with SAMPLENET_AMD_LIB=tools/_ab/libsamplenet_hip_tl.so).  Thread 0 of every chain workgroup stamps the
+"""Phase timeline of the two FC chain kernels inside the captured step (debug build: python samplenet_amd/build.py
+--timeline; run with SAMPLENET_AMD_LIB=tools/_ab/libsamplenet_hip_tl.so).  Thread 0 of every chain workgroup stamps the
 100 MHz wall clock at the phase boundaries; printed: per phase the median over the workgroups of (stamp - kernel's first stamp)."""
 import ctypes
 import os

@@ -4,7 +4,7 @@ launches them (queries produced by fc4 inside the scan, per-point minima combine
 with -DSN_PS_TIMELINE=L -DSN_CS_TIMELINE=L, L = 1 (stamps only) or 2 (every stamp first waits for the memory operations
 before it, i.e. serialised phases):
 
-    library built with those flags (pairscan.hip, sampler_step_loss.hip);   python tools/pairscan_timeline.py <that library> [B] [NET]
+    python samplenet_amd/build.py --timeline [--level 2];   python tools/pairscan_timeline.py tools/_ab/libsamplenet_hip_tl.so [B] [NET]
 
 Thread 0 of every workgroup stamps the 100 MHz wall clock; printed: median / p10 / p90 over the workgroups of the time
 between consecutive stamps, in microseconds.  In the loss backward lane 0 of EVERY wave also times its ordered owner sum (the

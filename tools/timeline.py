@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timeline of the MLP GEMM kernels on the GPU (debug build: tools/build_timeline_lib.sh).
+"""Phase timeline of the MLP GEMM kernels on the GPU (debug build: python samplenet_amd/build.py --timeline).
 Prints, per kernel shape, the distribution over workgroups of: start offset from the first workgroup,
 t(load landed in LDS), t(MFMA loop done), t(stores issued), t(stores drained), t(end) -- all in microseconds."""
 import ctypes
