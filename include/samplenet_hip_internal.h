@@ -885,6 +885,59 @@ int sn_group_pool_stats_blocks(int G);
 int sn_group_pool_backward(int G, int C, const float *g, const float *pooled, const float *zsel, float *gsel, float *stats,
                            sn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * A PointNet++ feature-propagation level around the GEMM entries above (csrc/feature_rows.hip; restated in numpy by
+ * tests/fp_rows_ref.py): the level's input in the ROW layout the GEMMs read, the gradient of its interpolated part by inverted
+ * index, and the backward of the walk's top activation with the top BatchNorm's partial sums.  The query stays sn_three_nn.
+ *
+ * sn_interp_rows_forward: known_rows (b,m,c2) ROW-major (channels contiguous); skip_rows (b,n,c1) row-major, or NULL with c1 == 0;
+ *   idx (b,n,3) int32 and dist2 (b,n,3) as sn_three_nn wrote them; rule 0: PointnetFPModule's 1 / (dist + 1e-8), 1: the TF module's
+ *   1 / max(dist^2, 1e-10) (tests/interp_ref.py: SQRT_EPS, SQUARED_CLAMP).  All fp32, every operation rounded once, nothing contracted:
+ *     r_t = 1 / (sqrtf(d2_t) + 1e-8f)  or  1 / fmaxf(d2_t, 1e-10f);  norm = (r_0 + r_1) + r_2;  w_t = r_t / norm
+ *   (sqrtf and the divisions correctly rounded; an unfilled slot's d2 = +inf gives weight 0).
+ *   weights (b,n,3), required (the backward reads it), and rows (b, n, c2 + c1) are fully OVERWRITTEN:
+ *     rows[b,j,ch] = ((w_0 * f[i_0,ch]) + (w_1 * f[i_1,ch])) + (w_2 * f[i_2,ch]) for ch < c2, f = known_rows[b], i_t = idx[b,j,t]:
+ *       the bits of sn_weighted_gather_forward at k = 3 given these weights;
+ *     rows[b,j,c2 + ch] = skip_rows[b,j,ch], copied bit for bit.
+ *   An index outside [0, m) is CLAMPED to the nearest of 0 and m - 1: nothing outside the cloud is read (sn_three_nn writes none).
+ *   One launch, no workspace, no atomics, capturable.  A group of LG lanes owns an output row, LG the power of two covering
+ *   c2 + c1, 64 at most, and walks the row's columns LG at a time; the row's weights are formed once, in front of that walk.
+ *   Checked on the host before any device work, in this order: a negative size, an unknown rule, c2 + c1 == 0 ->
+ *   SN_ERR_BAD_ARGUMENT; b == 0 or n == 0 is a no-op that succeeds; m == 0 with b * n > 0, a NULL required pointer (known_rows with
+ *   c2 > 0, skip_rows with c1 > 0, idx, dist2, weights, rows) -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1 workgroups
+ *   (ceil(b * n / (256 / LG))) -> SN_ERR_UNSUPPORTED.
+ *
+ * sn_interp_rows_backward: weights (b,n,3) as written above, grad_rows (b, n, c2 + c1); start (b,m+1) / order (b,3n) from
+ *   sn_gather_invert(b, m, 3 n, idx, ..) -> grad_known (b,m,c2), OVERWRITTEN:
+ *     grad_known[b,r,ch] = the fp32 sum over i in [start[b,r], start[b,r+1]), in that order and starting from +0, of
+ *     fl(grad_rows[b, e/3, ch] * weights[b,e]) with e = order[b,i]: the product rounded, then added, nothing contracted; a row with
+ *     no entry receives +0.  This is the arithmetic of sn_weighted_gather_backward_inverted: the two are BIT-IDENTICAL on transposed
+ *     operands.  The skip features' gradient is the view grad_rows[.., c2:] and needs no kernel; no gradient goes towards the
+ *     weights, the distances or the coordinates (sn_three_nn has none).
+ *   One launch: a group of LG lanes (the power of two covering c2, 64 at most) owns a row and LG of its columns, four entries'
+ *   loads in flight.  KNOWN LIMIT: lists are not split, so a launch takes as long as its longest list.  No atomics, no scratch,
+ *   capturable.  A start outside [0, 3n] is clamped and an entry number outside [0, 3n) skipped.
+ *   Checked on the host, in this order: a negative size, 3 n or c2 + c1 beyond 2^31 - 1 -> SN_ERR_BAD_ARGUMENT; b == 0, m == 0 or
+ *   c2 == 0 is a no-op that succeeds; start or grad_known NULL, or weights / grad_rows / order NULL with n > 0 ->
+ *   SN_ERR_BAD_ARGUMENT; more than 2^31 - 1 workgroups (ceil(b * m * ceil(c2 / LG) / (256 / LG))) -> SN_ERR_UNSUPPORTED.
+ *
+ * sn_bn_relu_backward_stats: dy (R, C) = sn_bn_relu_backward(R, C, z, coef, g, with_scale = 0, ..)'s output bit for bit, and in the
+ *   same launch the BatchNorm-backward partial sums stats [nblk][2][C], nblk = sn_bn_relu_stats_blocks(R) = ceil(R / 256), both
+ *   fully OVERWRITTEN: block k holds (sum dy, sum fl(dy * z)) over rows 256 k .. min(R, 256 k + 256) - 1 of every channel.  With
+ *   LR = the power of two covering C / 4, 64 at most, and S = 256 / LR slices: slice q adds the block's rows q, q + S, .. ascending
+ *   from +0, then the S slice sums are added in slice order from +0; every add rounded, nothing contracted.  The order depends on
+ *   R and C alone, never on the launch or on timing.  The layout is the one sn_bn_backward_coef(nblk, C, R, stats, ..) reduces.
+ *   No atomics, no workspace, capturable.  Checked on the host, in this order: a negative size, C % 4 != 0 ->
+ *   SN_ERR_BAD_ARGUMENT; R == 0 or C == 0 is a no-op that succeeds; a NULL pointer -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1
+ *   blocks -> SN_ERR_UNSUPPORTED (sn_bn_relu_stats_blocks returns 0 for R < 1 and beyond that bound). */
+int sn_interp_rows_forward(int b, int n, int m, int c2, int c1, int rule, const float *known_rows, const float *skip_rows,
+                           const int *idx, const float *dist2, float *weights, float *rows, sn_stream_t stream);
+int sn_interp_rows_backward(int b, int n, int m, int c2, int c1, const float *weights, const float *grad_rows, const int *start,
+                            const int *order, float *grad_known, sn_stream_t stream);
+int sn_bn_relu_stats_blocks(long long R);
+int sn_bn_relu_backward_stats(long long R, int C, const float *z, const float *coef, const float *g, float *dy, float *stats,
+                              sn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ SOURCES = [
     # the set abstraction's row-layout grouping shares the ball query's distance; its gradient and the group pool's partial sums
     # are written-out orders of rounded adds (tests/group_rows_ref.py restates them)
     ("set_abstraction.hip", ["-ffp-contract=off"]),
+    # the feature propagation's row assembly, its gradient and the top BatchNorm's partial sums: written-out orders (tests/fp_rows_ref.py)
+    ("feature_rows.hip", ["-ffp-contract=off"]),
 ]
 # No COMPILER-GENERATED packed fp32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in device code: with a SECOND process on the same GPU
 # (two ranks on one device, a monitoring job) kernels carrying the compiler's SLP-packed f32 ops returned wrong LOW halves in ~1 %

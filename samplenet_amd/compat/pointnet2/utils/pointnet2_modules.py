@@ -1,6 +1,6 @@
 """The modules of Pointnet2_PyTorch's pointnet2_modules, on the kernels of libsamplenet_hip.so:
 
-    PointnetFPModule(mlp, bn=True)(unknown (B,n,3), known (B,m,3), unknow_feats (B,C1,n) or None, known_feats (B,C2,m))
+    PointnetFPModule(mlp, bn=True, fused=False)(unknown (B,n,3), known (B,m,3), unknow_feats (B,C1,n) or None, known_feats (B,C2,m))
         -> (B, mlp[-1], n)
     PointnetSAModuleMSG(npoint, radii, nsamples, mlps, bn=True, use_xyz=True)(xyz (B,N,3), features (B,C,N) or None)
         -> (new_xyz (B,npoint,3), new_features (B, sum of mlp[-1], npoint))
@@ -10,7 +10,9 @@
 PointnetFPModule.forward reads as the original's: three_nn (sn_three_nn), the inverse-distance weights 1 / (dist + 1e-8) normalised
 over the three neighbours as torch operations, three_interpolate (sn_weighted_gather_forward at k = 3; the features' gradient by
 inverted index, ops.ThreeInterpolateFunction) and torch.cat with the skip features; the shared MLP behind them is plain torch: per
-layer a 1 x 1 Conv2d (with a bias only without BatchNorm), BatchNorm2d, ReLU, applied on unsqueeze(-1).
+layer a 1 x 1 Conv2d (with a bias only without BatchNorm), BatchNorm2d, ReLU, applied on unsqueeze(-1).  That is the default
+route; fused=True (opt-in) runs the level in the row layout on ops.interp_rows and the HIP GEMM walk
+(samplenet_amd.feature_propagation).
 
 The set-abstraction modules sample their centres with ops.furthest_point_sample, gather them (differentiable towards xyz), group
 every ball in the ROW layout (ops.ball_group_rows: one launch, a deterministic gradient by inverted index) and run the shared MLP
@@ -25,7 +27,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .... import ops, set_abstraction
+from .... import feature_propagation, ops, set_abstraction
 from . import pointnet2_utils
 
 
@@ -44,13 +46,24 @@ def shared_mlp(sizes, bn=True):
 
 
 class PointnetFPModule(nn.Module):
-    """Propagates the features of a sparse (known) cloud to a dense (unknown) one.  mlp: the layer widths, mlp[0] = C2 + C1."""
+    """Propagates the features of a sparse (known) cloud to a dense (unknown) one.  mlp: the layer widths, mlp[0] = C2 + C1.
+    fused (the constructor's default, or forward's keyword): with a known cloud and feature_propagation.fused_supported(self.mlp) the
+    level runs in the row layout -- sn_three_nn, ops.interp_rows (weights, interpolation and skip columns in one launch, a
+    deterministic gradient by inverted index) and the shared MLP on the HIP GEMM walk -- and returns (B, mlp[-1], n) as a transposed
+    VIEW of the walk's (B, n, mlp[-1]) rows, which the next fused level reads without a copy (.contiguous() gives channel-major
+    memory).  No gradient goes towards the coordinates on either route.  Anything else runs the default route."""
 
-    def __init__(self, mlp, bn=True):
+    def __init__(self, mlp, bn=True, fused=False):
         super().__init__()
         self.mlp = shared_mlp(list(mlp), bn=bn)
+        self.fused = bool(fused)
 
-    def forward(self, unknown, known, unknow_feats, known_feats):
+    def forward(self, unknown, known, unknow_feats, known_feats, fused=None):
+        fused = self.fused if fused is None else fused
+        if fused and known is not None and feature_propagation.fused_supported(self.mlp):
+            dist2, idx = ops.three_nn(unknown, known, return_dist2=True)
+            rows = ops.interp_rows(_rows_of(known_feats), None if unknow_feats is None else _rows_of(unknow_feats), idx, dist2)
+            return feature_propagation.propagate_mlp(self.mlp, rows).transpose(1, 2)
         if known is not None:
             dist, idx = ops.three_nn(unknown, known)
             dist_recip = 1.0 / (dist + 1e-8)

@@ -631,18 +631,20 @@ def _two_clouds(who, unknown, known):
         raise ValueError("%s: the known cloud is empty" % who)
 
 
-def three_nn(unknown, known):
+def three_nn(unknown, known, return_dist2=False):
     """The three nearest `known` points of every `unknown` point (no gradient): unknown (B,n,3), known (B,m,3) ->
     dist (B,n,3), the distances themselves (square roots, as Pointnet2_PyTorch's three_nn returns), and idx (B,n,3) int32,
-    ascending by (squared distance, index); with m < 3 the missing slots hold index 0 and an infinite distance (sn_three_nn)."""
+    ascending by (squared distance, index); with m < 3 the missing slots hold index 0 and an infinite distance (sn_three_nn).
+    return_dist2: -> (dist2, idx), the squared distances in place of their roots: what ops.interp_rows reads."""
     _need_gpu(unknown, known)
     unknown, known = _f32c(unknown.detach()), _f32c(known.detach())
     _two_clouds("three_nn", unknown, known)
     b, n, _ = unknown.shape
     dist = torch.empty(b, n, 3, device=unknown.device, dtype=torch.float32)
     idx = torch.empty(b, n, 3, device=unknown.device, dtype=torch.int32)
+    d2, d = (dist, None) if return_dist2 else (None, dist)
     with torch.cuda.device(unknown.device):
-        check(lib.sn_three_nn(b, n, known.shape[1], ptr(unknown), ptr(known), None, ptr(dist), ptr(idx), _stream(unknown)), "sn_three_nn")
+        check(lib.sn_three_nn(b, n, known.shape[1], ptr(unknown), ptr(known), ptr(d2), ptr(d), ptr(idx), _stream(unknown)), "sn_three_nn")
     return dist, idx
 
 
@@ -748,6 +750,104 @@ def three_interpolate(features, idx, weight, inverse=None):
                              % (name, shape, m, tuple(t.shape), t.dtype))
     _one_device("three_interpolate", features, start, order)
     return ThreeInterpolateFunction.apply(features, idx, weight, start, order)
+
+
+INTERP_RULES = {"sqrt_eps": 0, "squared_clamp": 1}  # sn_interp_rows_forward's rule
+
+
+class InterpRowsFunction(torch.autograd.Function):
+    """known_rows (B,m,C2), skip_rows (B,n,C1) or None, both row-major, idx / dist2 (B,n,3) of sn_three_nn -> rows (B,n,C2+C1)
+    (sn_interp_rows_forward).  Backward: towards known_rows by inverted index (sn_gather_invert + sn_interp_rows_backward; beyond
+    sn_gather_invert_supported the ordered route on the transposed slice, the same bits), towards skip_rows the view
+    grad_rows[..., C2:].  No gradient goes towards the weights, the distances or the coordinates: three_nn has none and the module's
+    weights carry none."""
+
+    @staticmethod
+    def forward(ctx, known_rows, skip_rows, idx, dist2, rule, start, order):
+        known_rows, dist2 = _f32c(known_rows), _f32c(dist2)
+        skip_rows = None if skip_rows is None else _f32c(skip_rows)
+        idx = idx.contiguous().int()
+        b, m, c2 = known_rows.shape
+        n = idx.shape[1]
+        c1 = 0 if skip_rows is None else skip_rows.shape[2]
+        weights = torch.empty(b, n, 3, device=known_rows.device, dtype=torch.float32)
+        rows = torch.empty(b, n, c2 + c1, device=known_rows.device, dtype=torch.float32)
+        with torch.cuda.device(known_rows.device):
+            check(lib.sn_interp_rows_forward(b, n, m, c2, c1, rule, ptr(known_rows), ptr(skip_rows), ptr(idx), ptr(dist2), ptr(weights),
+                                             ptr(rows), _stream(known_rows)), "sn_interp_rows_forward")
+        ctx.save_for_backward(known_rows, idx, weights, start, order)
+        ctx.dims = (b, n, m, c2, c1)
+        return rows
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        known_rows, idx, weights, start, order = ctx.saved_tensors
+        b, n, m, c2, c1 = ctx.dims
+        grad_rows = _f32c(grad_rows)
+        dev = grad_rows.device
+        gk = None
+        gs = grad_rows[..., c2:] if c1 > 0 and ctx.needs_input_grad[1] else None
+        if ctx.needs_input_grad[0]:
+            with torch.cuda.device(dev):
+                st = _stream(grad_rows)
+                if start is None and not gather_invert_supported(m, 3 * n):
+                    # the ordered route reads and writes channel-major: the transposed slice in, the transposed gradient out
+                    g = grad_rows[..., :c2].transpose(1, 2).contiguous()
+                    X = known_rows.transpose(1, 2).contiguous()
+                    gX = torch.empty(b, c2, m, device=dev, dtype=torch.float32)
+                    scratch = torch.empty(b * c2 * n * 3, device=dev, dtype=torch.float32)
+                    check(lib.sn_weighted_gather_backward_ordered(b, c2, m, n, 3, ptr(X), ptr(idx), ptr(weights), ptr(g), None, ptr(gX),
+                                                                  ptr(scratch), st), "sn_weighted_gather_backward_ordered")
+                    gk = gX.transpose(1, 2).contiguous()
+                else:
+                    if start is None:
+                        start, order = gather_invert(idx, m)
+                    gk = torch.empty(b, m, c2, device=dev, dtype=torch.float32)
+                    check(lib.sn_interp_rows_backward(b, n, m, c2, c1, ptr(weights), ptr(grad_rows), ptr(start), ptr(order), ptr(gk), st),
+                          "sn_interp_rows_backward")
+        return gk, gs, None, None, None, None, None
+
+
+def interp_rows(known_rows, skip_rows, idx, dist2, rule="sqrt_eps", inverse=None):
+    """The input of a feature-propagation level in the row layout the GEMM entries read, in one launch: known_rows (B,m,C2) and
+    skip_rows (B,n,C1) or None, both ROW-major (channels contiguous), idx (B,n,3) int32 and dist2 (B,n,3) from
+    ops.three_nn(.., return_dist2=True) -> rows (B, n, C2 + C1): columns 0 .. C2-1 the inverse-distance interpolation of the three
+    neighbours' rows (rule "sqrt_eps": weights 1 / (dist + 1e-8), PointnetFPModule's; "squared_clamp": 1 / max(dist^2, 1e-10),
+    normalised over the three), bit for bit ops.three_interpolate on these weights, then the C1 skip columns copied.
+    Differentiable towards known_rows (the deterministic ordered sum by inverted index; inverse: ops.gather_invert(idx, m) of THIS
+    idx for a caller that reuses it, else every backward builds it; beyond ops.gather_invert_supported(m, 3 n) the ordered route
+    serves and no inverse exists) and towards skip_rows (a view of the incoming gradient).  No gradient goes towards the weights,
+    the distances or the coordinates: three_nn has none and the module's weights carry none."""
+    _need_gpu(known_rows, skip_rows, idx, dist2)
+    if rule not in INTERP_RULES:
+        raise ValueError("interp_rows: rule must be one of %s, got %r" % (sorted(INTERP_RULES), rule))
+    if known_rows.dim() != 3 or idx.dim() != 3 or idx.shape[2] != 3 or tuple(dist2.shape) != tuple(idx.shape) or idx.shape[0] != known_rows.shape[0]:
+        raise ValueError("interp_rows: known_rows must be (B,m,C2), idx and dist2 (B,n,3)")
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("interp_rows: idx must be int32 (or int64, converted), got %s" % idx.dtype)
+    b, m, c2 = known_rows.shape
+    n = idx.shape[1]
+    if skip_rows is not None and (skip_rows.dim() != 3 or skip_rows.shape[0] != b or skip_rows.shape[1] != n):
+        raise ValueError("interp_rows: skip_rows must be (B,n,C1), got %s" % (tuple(skip_rows.shape),))
+    if skip_rows is not None and skip_rows.shape[2] == 0:
+        skip_rows = None
+    if c2 + (0 if skip_rows is None else skip_rows.shape[2]) == 0:
+        raise ValueError("interp_rows: no output column (C2 + C1 == 0)")
+    if m == 0 and b * n > 0:
+        raise ValueError("interp_rows: the known cloud is empty")
+    _one_device("interp_rows", known_rows, skip_rows, idx, dist2)
+    start = order = None
+    if inverse is not None:
+        start, order = inverse
+        if not gather_invert_supported(m, n * 3):
+            raise ValueError("interp_rows: m = %d with %d entries per cloud is beyond sn_gather_invert_supported: no inverse exists "
+                             "for it (leave inverse=None for the ordered route)" % (m, n * 3))
+        for t, shape, name in ((start, (b, m + 1), "start"), (order, (b, n * 3), "order")):
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError("interp_rows: inverse.%s must be contiguous int32 %s (ops.gather_invert(idx, %d)), got %s %s"
+                                 % (name, shape, m, tuple(t.shape), t.dtype))
+        _one_device("interp_rows", known_rows, start, order)
+    return InterpRowsFunction.apply(known_rows, skip_rows, idx, dist2, INTERP_RULES[rule], start, order)
 
 
 # --------------------------------------------------------------------------------------------- set abstraction: row-layout grouping

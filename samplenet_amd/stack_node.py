@@ -6,6 +6,7 @@ set-abstraction MLP share.  What the callers do differently is a StackSpec, noth
     classifier       POINTS / NONE  None                       a parameter asks        raises
     autoencoder      POINTS         the module (CONV_STACK)    a parameter asks        None: fixed statistics, allowed
     set abstraction  POINTS/GROUPS  None                       the module is training  raises
+    feature propag.  ROWS           None                       the module is training  raises
 
 A layer without a bias (L.b is None) gets NULL in the GEMMs and a scratch entry in the walk's sink for the bias-gradient output the
 kernels write in any case.  Parameters: pointnet.stack_params(layers), gradients returned in that order.
@@ -21,6 +22,7 @@ from ._lib import check, lib, ptr, stream_of
 POOL_POINTS = "points"  # sn_pool_forward / sn_pool_backward_bn (a workgroup per group)
 POOL_GROUPS = "groups"  # sn_group_pool_forward / sn_group_pool_backward + sn_bn_backward_coef (a wave per group and 64 channels)
 POOL_NONE = "none"      # the activated rows themselves: sn_bn_relu_forward / _backward, torch sums for the top BatchNorm
+POOL_ROWS = "rows"      # POOL_NONE's forward; backward: sn_bn_relu_backward_stats, dY and the top BatchNorm's sums in one launch
 # walk_wgrads: when the backward walk is the one that also forms weight gradients
 WGRADS_ASKED = "asked"        # a parameter asks for a gradient
 WGRADS_TRAINING = "training"  # the forward ran on batch statistics, frozen parameters or not
@@ -50,7 +52,7 @@ class _ConvStackFunction(torch.autograd.Function):
         saved = {"x": x, "B": G, "N": S}
         argsel = None
         with torch.cuda.device(x.device):
-            if spec.pool == POOL_NONE:
+            if spec.pool in (POOL_NONE, POOL_ROWS):
                 saved["zc"], saved["cc"] = pointnet._conv_stack_fwd(layers, x, training, None)
                 out = torch.empty(G, S, Co, device=x.device, dtype=torch.float32)
                 check(lib.sn_bn_relu_forward(G * S, Co, ptr(saved["zc"][-1]), ptr(saved["cc"][-1]), ptr(out), stream_of(x)),
@@ -103,10 +105,16 @@ class _ConvStackFunction(torch.autograd.Function):
                     stats = None if fixed else torch.empty(nblk, 2, C, device=g.device, dtype=torch.float32)
                     check(lib.sn_group_pool_backward(G, C, ptr(g), ptr(saved["pooled"]), ptr(saved["zsel"]), ptr(gsel), ptr(stats),
                                                      stream_of(g)), "sn_group_pool_backward")
+                elif spec.pool == POOL_ROWS and not fixed:
+                    dy = torch.empty(R, C, device=g.device, dtype=torch.float32)
+                    nblk = lib.sn_bn_relu_stats_blocks(R)
+                    stats = torch.empty(nblk, 2, C, device=g.device, dtype=torch.float32)
+                    check(lib.sn_bn_relu_backward_stats(R, C, ptr(z), ptr(coef), ptr(g), ptr(dy), ptr(stats), stream_of(g)),
+                          "sn_bn_relu_backward_stats")
                 else:
                     dy = torch.empty(R, C, device=g.device, dtype=torch.float32)
                     check(lib.sn_bn_relu_backward(R, C, ptr(z), ptr(coef), ptr(g), 0, ptr(dy), stream_of(g)), "sn_bn_relu_backward")
-                    if not fixed:
+                    if not fixed:  # (POOL_NONE)
                         # (sum dY, sum dY Z) of the top BatchNorm as ONE block of partials; training mode need not be fast
                         stats, nblk = torch.stack((dy.sum(0), (dy * z).sum(0))).view(1, 2, C).contiguous(), 1
                 if fixed:
