@@ -822,15 +822,22 @@ int sn_three_nn(int b, int n, int m, const float *unknown, const float *known, f
  *   Checked on the host before any device work, in this order: a negative size -> SN_ERR_BAD_ARGUMENT; b == 0 or n == 0 is a
  *   no-op that succeeds; start NULL, or idx / order NULL with ne > 0 -> SN_ERR_BAD_ARGUMENT; the bound.
  *
+ * THE LIST WALK, shared by the three gradients that consume start / order (sn_weighted_gather_backward_inverted here,
+ *   sn_group_rows_backward and sn_interp_rows_backward below; csrc/inverse_walk.h holds the row-layout kernels' one body): an output
+ *   element of destination row r is the fp32 sum over i in [start[b,r], start[b,r+1]), in that order and starting from +0, of one
+ *   term per entry e = order[b,i]; a weighted term is fl(gradient * weights[b,e]), the product rounded, then added; every add is
+ *   rounded, nothing is contracted.  A row with no entry receives +0.  On lists of sn_gather_invert the order is ascending entry
+ *   number, which is the order of sn_weighted_gather_backward_ordered.  CLAMP AND SKIP: a start outside [0, ne] is clamped and an
+ *   entry number outside [0, ne) skipped, so foreign buffers cannot make a walk read elsewhere.  KNOWN LIMIT: lists are not split
+ *   (that would change the order), so a launch takes as long as its longest list.  No atomics, no scratch, capturable.
+ *
  * sn_weighted_gather_backward_inverted: weights (b,m,k), grad_out (b,c,m), start / order as above -> grad_X (b,c,n), OVERWRITTEN:
- *   grad_X[b,ch,r] = the fp32 sum over i in [start[b,r], start[b,r+1]), in that order and starting from +0, of
- *   fl(grad_out[b,ch,e/k] * weights[b,e]) with e = order[b,i]: the product rounded, then added, nothing contracted.  A row with no
- *   entry receives +0.  This is the arithmetic of sn_weighted_gather_backward_ordered: with start / order from sn_gather_invert on
- *   the same idx the two grad_X are BIT-IDENTICAL.  idx itself is not an argument: the lists carry all it says.  The gradient towards
- *   the weights stays with sn_weighted_gather_backward (grad_X = NULL).
+ *   grad_X[b,ch,r] = the list walk's sum of fl(grad_out[b,ch,e/k] * weights[b,e]) (ne = m*k).  This is the arithmetic of
+ *   sn_weighted_gather_backward_ordered: with start / order from sn_gather_invert on the same idx the two grad_X are BIT-IDENTICAL.
+ *   idx itself is not an argument: the lists carry all it says.  The gradient towards the weights stays with
+ *   sn_weighted_gather_backward (grad_X = NULL).
  *   One launch: a thread owns one row and 8 channels of it (entry number, query and weight loaded once per entry for the 8
- *   accumulators); lists are not split, so a launch takes as long as its longest list.  No atomics, no scratch, capturable.
- *   A start outside [0, m*k] is clamped and an entry number outside [0, m*k) skipped: foreign buffers cannot make it read elsewhere.
+ *   accumulators).
  *   Checked on the host: a negative size, k < 1, m * k beyond 2^31 - 1 -> SN_ERR_BAD_ARGUMENT; b == 0, c == 0 or n == 0 is a no-op
  *   that succeeds; start or grad_X NULL, or weights / grad_out / order NULL with m > 0 -> SN_ERR_BAD_ARGUMENT; more than 2^31 - 1
  *   workgroups (b * ceil(n * ceil(c / 8) / 256)) -> SN_ERR_UNSUPPORTED. */
@@ -856,11 +863,9 @@ int sn_weighted_gather_backward_inverted(int b, int c, int n, int m, int k, cons
  * sn_group_rows_backward: grad_rows (b, m*nsample, 3 use_xyz + c); start (b,n+1) / order (b, m*nsample) from
  *   sn_gather_invert(b, n, m*nsample, idx, ..).  idx itself is not read (the lists carry all it says) and may be NULL.  Each output
  *   may be NULL; one that is NULL is not touched, the others are OVERWRITTEN:
- *   grad_features (b,n,c), grad_xyz (b,n,3): element [b,r,ch] = the fp32 sum, from +0, over i in [start[b,r], start[b,r+1]) in that
- *       order (ascending entry number) of grad_rows[b, order[b,i], col]; every add rounded, nothing contracted; a row with an empty
- *       list gets +0.  No atomics, one order: the bits repeat.  A start outside [0, m*nsample] is clamped and an entry number outside
- *       [0, m*nsample) skipped.  KNOWN LIMIT: lists are not split, so a launch takes as long as its longest list -- and point 0
- *       collects every empty ball;
+ *   grad_features (b,n,c), grad_xyz (b,n,3): element [b,r,ch] = THE LIST WALK's sum (above; ne = m*nsample) of the unweighted
+ *       terms grad_rows[b, e, col].  No atomics, one order: the bits repeat.  Its known limit bites here: point 0 collects every
+ *       empty ball;
  *   grad_new_xyz (b,m,3): -(sum over s of grad_rows[b, j*nsample + s, 0:3]) in sn_ball_group_backward's order (lane l adds slots l,
  *       l + 64, .. ascending, the xor tree 32 .. 1, one negation): bit-identical to that entry on the permuted gradient.
  *   Without use_xyz the two point gradients are zeros.  Up to two launches, no workspace, capturable.  Checked on the host: a
@@ -909,14 +914,12 @@ int sn_group_pool_backward(int G, int C, const float *g, const float *pooled, co
  *
  * sn_interp_rows_backward: weights (b,n,3) as written above, grad_rows (b, n, c2 + c1); start (b,m+1) / order (b,3n) from
  *   sn_gather_invert(b, m, 3 n, idx, ..) -> grad_known (b,m,c2), OVERWRITTEN:
- *     grad_known[b,r,ch] = the fp32 sum over i in [start[b,r], start[b,r+1]), in that order and starting from +0, of
- *     fl(grad_rows[b, e/3, ch] * weights[b,e]) with e = order[b,i]: the product rounded, then added, nothing contracted; a row with
- *     no entry receives +0.  This is the arithmetic of sn_weighted_gather_backward_inverted: the two are BIT-IDENTICAL on transposed
- *     operands.  The skip features' gradient is the view grad_rows[.., c2:] and needs no kernel; no gradient goes towards the
- *     weights, the distances or the coordinates (sn_three_nn has none).
+ *     grad_known[b,r,ch] = THE LIST WALK's sum (above; ne = 3n) of the weighted terms fl(grad_rows[b, e/3, ch] * weights[b,e]).
+ *     This is the arithmetic of sn_weighted_gather_backward_inverted: the two are BIT-IDENTICAL on transposed operands.  The skip
+ *     features' gradient is the view grad_rows[.., c2:] and needs no kernel; no gradient goes towards the weights, the distances or
+ *     the coordinates (sn_three_nn has none).
  *   One launch: a group of LG lanes (the power of two covering c2, 64 at most) owns a row and LG of its columns, four entries'
- *   loads in flight.  KNOWN LIMIT: lists are not split, so a launch takes as long as its longest list.  No atomics, no scratch,
- *   capturable.  A start outside [0, 3n] is clamped and an entry number outside [0, 3n) skipped.
+ *   loads in flight.
  *   Checked on the host, in this order: a negative size, 3 n or c2 + c1 beyond 2^31 - 1 -> SN_ERR_BAD_ARGUMENT; b == 0, m == 0 or
  *   c2 == 0 is a no-op that succeeds; start or grad_known NULL, or weights / grad_rows / order NULL with n > 0 ->
  *   SN_ERR_BAD_ARGUMENT; more than 2^31 - 1 workgroups (ceil(b * m * ceil(c2 / LG) / (256 / LG))) -> SN_ERR_UNSUPPORTED.

@@ -267,10 +267,9 @@ __global__ void __launch_bounds__(kGbThreads) gather_bwd_inverted_kernel(int c, 
     float acc[kGbChannels];
 #pragma unroll
     for (int q = 0; q < kGbChannels; ++q) acc[q] = 0.f;
-    // (a start outside [0, ne] or an entry number outside [0, ne) can only come from a caller's own buffers: nothing is read there)
+    // inverse_walk.h's walk, clamp-and-skip rule included, on the channel-major layout with a run-time k and kGbChannels sums per
+    // thread (two memory latencies per batch instead of per entry)
     const int lo = max(start[row], 0), hi = min(start[row + 1], ne);
-    // kGbBatch entries at a time: their entry numbers, then their weights and gradients, are loaded side by side (two memory
-    // latencies per batch instead of per entry); the sums still take the entries one by one, in list order
     for (int i = lo; i < hi; i += kGbBatch) {
         int e[kGbBatch];
         float wt[kGbBatch], gv[kGbBatch][kGbChannels];

@@ -9,30 +9,21 @@
 //     row one contiguous run of c1.  The row's three indices, distances and weights are formed once, in front of the column walk,
 //     from loads every lane of the group makes at the same address (one transaction); the group's first lane stores the weights.
 // sn_interp_rows_backward     a group of LG lanes (the power of two covering c2, 64 at most) owns a destination row of the known cloud
-//     and LG of its columns, walks the row's list of sn_gather_invert in list order and adds fl(grad_rows[e / 3, col] * weights[e])
-//     from +0: every read of an entry is one contiguous segment, four entries' loads are in flight, the sums take the entries one by
-//     one.  Lists are not split: a launch takes as long as its longest list.
+//     and LG of its columns and takes inverse_walk.h's weighted sum over the row's list, three entries to a source row: the terms are
+//     fl(grad_rows[e / 3, col] * weights[e]), every read of an entry one contiguous segment.
 // sn_bn_relu_backward_stats   dy = g . [relu(scale z + shift) > 0] as sn_bn_relu_backward writes it, and (sum dy, sum fl(dy * z))
 //     over blocks of kBsRows rows, each in one fixed order: the layout sn_bn_backward_coef reduces.
 // No workspace, no atomics: deterministic, safe under stream capture.
-#include <climits>
 #include <cmath>
 
-#include "sn_common.h"
+#include "inverse_walk.h"
 
 #pragma clang fp contract(off)  // every product and sum of the contracts is rounded on its own (the activation's one fmaf is written out)
 
 namespace sn {
 namespace {
 
-constexpr int kFrThreads = 256;
-
-int lane_group(long long cols)
-{
-    int lg = 1;
-    while (lg < cols && lg < kWave) lg <<= 1;
-    return lg;
-}
+constexpr int kFrThreads = kLaneThreads;
 
 // ------------------------------------------------------------------------------------------------ the assembly
 struct InterpArgs {
@@ -86,8 +77,6 @@ __global__ void __launch_bounds__(kFrThreads) interp_rows_kernel(const InterpArg
 }
 
 // ------------------------------------------------------------------------------------------------ its gradient
-constexpr int kIbBatch = 4;  // entries of a list whose loads are in flight together
-
 struct InterpGradArgs {
     int m, ne, c2, Ci, lg, chunks;
     long long items;              // b * m * chunks (row, chunk) pairs
@@ -113,25 +102,7 @@ __global__ void __launch_bounds__(kFrThreads) interp_rows_backward_kernel(const 
     const int *order = a.order + (size_t)cloud * a.ne;
     const float *w = a.weights + (size_t)cloud * a.ne;
     const float *g = a.grad_rows + (size_t)cloud * (a.ne / 3) * a.Ci + col;
-    // (a start outside [0, ne] or an entry number outside [0, ne) can only come from a caller's own buffers: nothing is read there)
-    const int lo = max(start[0], 0), hi = min(start[1], a.ne);
-    float acc = 0.f;
-    for (int i = lo; i < hi; i += kIbBatch) {
-        int e[kIbBatch];
-        float wt[kIbBatch], gv[kIbBatch];
-#pragma unroll
-        for (int t = 0; t < kIbBatch; ++t) e[t] = i + t < hi ? order[i + t] : -1;
-#pragma unroll
-        for (int t = 0; t < kIbBatch; ++t) {
-            const unsigned at = (unsigned)e[t] < (unsigned)a.ne ? (unsigned)e[t] : 0u;   // (an entry that is skipped below reads entry 0's operands)
-            wt[t] = w[at];
-            gv[t] = g[(size_t)(at / 3u) * a.Ci];
-        }
-#pragma unroll
-        for (int t = 0; t < kIbBatch; ++t)
-            if ((unsigned)e[t] < (unsigned)a.ne) acc += gv[t] * wt[t];   // product rounded, then added: gather_bwd_inverted_kernel's
-    }
-    a.grad_known[rowi * a.c2 + col] = acc;
+    a.grad_known[rowi * a.c2 + col] = inverse_walk_sum<3, true>(start, order, a.ne, g, a.Ci, w);
 }
 
 // ------------------------------------------------------------------------------------------------ top activation backward + sums
@@ -216,14 +187,13 @@ extern "C" int sn_interp_rows_forward(int b, int n, int m, int c2, int c1, int r
     if (b == 0 || n == 0) return 0;
     SN_REQUIRE(m >= 1, "an empty known cloud (m == 0) has no row to read");
     SN_REQUIRE(idx && dist2 && weights && rows && (c2 == 0 || known_rows) && (c1 == 0 || skip_rows), "null pointer");
+    LaneGrid l;
+    if (int rc = lane_grid(__func__, (long long)b * n, c2 + c1, false, &l)) return rc;
     InterpArgs a = {};
-    a.m = m, a.c2 = c2, a.c1 = c1, a.rule = rule, a.lg = lane_group((long long)c2 + c1);
-    a.rows = (long long)b * n, a.n = n;
+    a.m = m, a.c2 = c2, a.c1 = c1, a.rule = rule, a.lg = l.lg;
+    a.rows = l.items, a.n = n;
     a.known_rows = known_rows, a.skip_rows = skip_rows, a.idx = idx, a.dist2 = dist2, a.weights = weights, a.out = rows;
-    const int per = kFrThreads / a.lg;
-    const long long grid = (a.rows + per - 1) / per;
-    if (grid > INT_MAX) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
-    hipLaunchKernelGGL(interp_rows_kernel, dim3((unsigned)grid), dim3(kFrThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(interp_rows_kernel, dim3(l.grid), dim3(kFrThreads), 0, (hipStream_t)stream, a);
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -235,15 +205,12 @@ extern "C" int sn_interp_rows_backward(int b, int n, int m, int c2, int c1, cons
     SN_REQUIRE(3ll * n <= INT_MAX && (long long)c2 + c1 <= INT_MAX, "3 n and c2 + c1 must fit in 31 bits");
     if (b == 0 || m == 0 || c2 == 0) return 0;
     SN_REQUIRE(start && grad_known && (n == 0 || (weights && grad_rows && order)), "null pointer");
+    LaneGrid l;
+    if (int rc = lane_grid(__func__, (long long)b * m, c2, true, &l)) return rc;
     InterpGradArgs a = {};
-    a.m = m, a.ne = 3 * n, a.c2 = c2, a.Ci = c2 + c1, a.lg = lane_group(c2);
-    a.chunks = (c2 + a.lg - 1) / a.lg;
-    a.items = (long long)b * m * a.chunks;
+    a.m = m, a.ne = 3 * n, a.c2 = c2, a.Ci = c2 + c1, a.lg = l.lg, a.chunks = l.chunks, a.items = l.items;
     a.weights = weights, a.grad_rows = grad_rows, a.start = start, a.order = order, a.grad_known = grad_known;
-    const int per = kFrThreads / a.lg;
-    const long long grid = (a.items + per - 1) / per;
-    if (grid > INT_MAX) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
-    hipLaunchKernelGGL(interp_rows_backward_kernel, dim3((unsigned)grid), dim3(kFrThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(interp_rows_backward_kernel, dim3(l.grid), dim3(kFrThreads), 0, (hipStream_t)stream, a);
     SN_LAUNCH_CHECK();
     return 0;
 }
@@ -259,7 +226,7 @@ extern "C" int sn_bn_relu_backward_stats(long long R, int C, const float *z, con
     SN_REQUIRE(z && coef && g && dy && stats, "null pointer");
     const int lr = lane_group(C / 4);
     const int nblk = sn_bn_relu_stats_blocks(R), cblocks = (C / 4 + lr - 1) / lr;
-    if (nblk == 0) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
+    if (nblk == 0) return sn_too_many_workgroups(__func__);
     SN_REQUIRE(cblocks <= 65535, "C beyond 65535 * 256 channels");
     hipLaunchKernelGGL(bn_relu_bwd_stats_kernel, dim3((unsigned)nblk, (unsigned)cblocks), dim3(kFrThreads), 0, (hipStream_t)stream, R, C, lr, z,
                        coef, g, dy, stats);

@@ -9,17 +9,17 @@
 //     copied from one contiguous feature row, so the wave walks the group's nsample * Ci output floats FLAT over its lanes: stores
 //     are fully coalesced, loads are runs of Ci floats; four rounds (256 floats) are loaded before the first is stored.
 // sn_group_rows_backward       grad_features / grad_xyz: a group of LG lanes (the power of two covering the columns, 64 at most)
-//     owns a destination row and LG of its columns, walks the row's list of sn_gather_invert in list order (ascending entry number)
-//     and adds grad_rows[e, col] from +0: every read of an entry is one contiguous segment, four entries' loads are in flight, the
-//     sums take the entries one by one.  Lists are not split: a launch takes as long as its longest list, and point 0 collects every
-//     empty ball.  grad_new_xyz: sn_ball_group_backward's order (lane l adds slots l, l + 64, .. ascending, xor tree 32 .. 1, one
-//     negation) on the row layout.
+//     owns a destination row and LG of its columns and takes inverse_walk.h's unweighted sum over the row's list: the terms are
+//     grad_rows[e, col], every read of an entry one contiguous segment.  Point 0 collects every empty ball, so its list is the
+//     launch's longest.  grad_new_xyz: sn_ball_group_backward's order (lane l adds slots l, l + 64, .. ascending, xor tree 32 .. 1,
+//     one negation) on the row layout.
 // sn_group_pool_forward        a wave per (group, 64 channels), four of them per workgroup, rows ascending with four loads in
 //     flight: the first row wins a tie because a later row replaces the pick only when strictly greater (smaller).
 // sn_group_pool_backward       gsel = g * [pooled > 0] and the BatchNorm-backward partial sums as blocks of kGpGroups groups, each
 //     summed in one fixed order: the layout sn_bn_backward_coef reduces.
 // No LDS but the pool backward's 2 KB, no workspace, no atomics: deterministic, safe under stream capture.
 #include "ball_scan.h"
+#include "inverse_walk.h"
 
 #pragma clang fp contract(off)  // every sum below is add after add, every product rounded (the pool's one fmaf is written out)
 
@@ -93,8 +93,7 @@ __global__ void __launch_bounds__(kBallWaves *kWave) ball_group_rows_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------------ its gradient
-constexpr int kGrThreads = 256;
-constexpr int kGrBatch = 4;  // entries of a list whose loads are in flight together
+constexpr int kGrThreads = kLaneThreads;
 
 struct GradRowsArgs {
     int n, ne, Ci, c, u3;
@@ -123,20 +122,7 @@ __global__ void __launch_bounds__(kGrThreads) group_rows_backward_kernel(const G
     const int *start = a.start + rowi + cloud;               // cloud * (n + 1) + r
     const int *order = a.order + (size_t)cloud * a.ne;
     const float *g = a.grad_rows + (size_t)cloud * a.ne * a.Ci + col;
-    // (a start outside [0, ne] or an entry number outside [0, ne) can only come from a caller's own buffers: nothing is read there)
-    const int lo = max(start[0], 0), hi = min(start[1], a.ne);
-    float acc = 0.f;
-    for (int i = lo; i < hi; i += kGrBatch) {
-        int e[kGrBatch];
-        float v[kGrBatch];
-#pragma unroll
-        for (int t = 0; t < kGrBatch; ++t) e[t] = i + t < hi ? order[i + t] : -1;
-#pragma unroll
-        for (int t = 0; t < kGrBatch; ++t) v[t] = g[(size_t)((unsigned)e[t] < (unsigned)a.ne ? e[t] : 0) * a.Ci];  // (skipped below)
-#pragma unroll
-        for (int t = 0; t < kGrBatch; ++t)
-            if ((unsigned)e[t] < (unsigned)a.ne) acc += v[t];   // list order, one rounded add per entry
-    }
+    const float acc = inverse_walk_sum<1, false>(start, order, a.ne, g, a.Ci, nullptr);
     if (col < a.u3)
         a.grad_xyz[rowi * 3 + col] = acc;
     else
@@ -324,15 +310,11 @@ extern "C" int sn_group_rows_backward(int b, int n, int m, int c, int nsample, i
         a.n = n, a.ne = ne, a.Ci = Ci, a.c = c, a.u3 = u3;
         a.col0 = grad_xyz ? 0 : u3;
         a.ncols = (grad_features ? Ci : u3) - a.col0;
-        a.lg = 1;
-        while (a.lg < a.ncols && a.lg < kWave) a.lg <<= 1;
-        a.chunks = (a.ncols + a.lg - 1) / a.lg;
-        a.items = (long long)b * n * a.chunks;
+        LaneGrid l;
+        if (int rc = lane_grid(__func__, (long long)b * n, a.ncols, true, &l)) return rc;
+        a.lg = l.lg, a.chunks = l.chunks, a.items = l.items;
         a.start = start, a.order = order, a.grad_rows = grad_rows, a.grad_features = grad_features, a.grad_xyz = grad_xyz;
-        const int per = kGrThreads / a.lg;
-        const long long grid = (a.items + per - 1) / per;
-        if (grid > INT_MAX) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
-        hipLaunchKernelGGL(group_rows_backward_kernel, dim3((unsigned)grid), dim3(kGrThreads), 0, st, a);
+        hipLaunchKernelGGL(group_rows_backward_kernel, dim3(l.grid), dim3(kGrThreads), 0, st, a);
     }
     if (grad_new_xyz && m > 0) {
         GradCentreArgs a = {};
@@ -351,7 +333,7 @@ extern "C" int sn_group_pool_forward(int G, int S, int C, const float *z, const 
     SN_REQUIRE(G >= 1 && S >= 1 && C >= 1 && z && coef && pooled && argsel && zsel, "bad argument");
     const int cblocks = (C + kWave - 1) / kWave;
     const long long items = (long long)G * cblocks, grid = (items + kGpWaves - 1) / kGpWaves;
-    if (grid > INT_MAX) return sn_set_error(SN_ERR_UNSUPPORTED, "%s: the launch needs more than 2^31 - 1 workgroups", __func__);
+    if (grid > INT_MAX) return sn_too_many_workgroups(__func__);
     hipLaunchKernelGGL(group_pool_fwd_kernel, dim3((unsigned)grid), dim3(kGpWaves * kWave), 0, (hipStream_t)stream, items, cblocks, S, C, z,
                        coef, pooled, argsel, zsel);
     SN_LAUNCH_CHECK();

@@ -680,6 +680,33 @@ def gather_invert(idx, n):
     return GatherInverse(start, order)
 
 
+def _inverse_arg(who, inverse, b, n, ne, like):
+    """The inverse= of `who`, checked against b clouds of n destination rows and ne entries on `like`'s device -> (start, order);
+    (None, None) for None."""
+    if inverse is None:
+        return None, None
+    start, order = inverse
+    if not gather_invert_supported(n, ne):
+        raise ValueError("%s: m = %d with %d entries per cloud is beyond sn_gather_invert_supported: no inverse exists "
+                         "for it (leave inverse=None for the ordered route)" % (who, n, ne))
+    for t, shape, name in ((start, (b, n + 1), "start"), (order, (b, ne), "order")):
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("%s: inverse.%s must be contiguous int32 %s (ops.gather_invert(idx, %d)), got %s %s"
+                             % (who, name, shape, n, tuple(t.shape), t.dtype))
+    _one_device(who, like, start, order)
+    return start, order
+
+
+def _backward_inverse(idx, n, start=None, order=None):
+    """The lists a backward by inverted index walks: the pair its forward was given, else one built now (sn_gather_invert), else --
+    beyond gather_invert_supported -- None, and the node takes its own fallback route."""
+    if start is not None:
+        return start, order
+    if not gather_invert_supported(n, idx.shape[1:].numel()):
+        return None
+    return gather_invert(idx, n)
+
+
 class ThreeInterpolateFunction(torch.autograd.Function):
     """WeightedGatherFunction's forward; the gradient towards the features by inverted index (sn_gather_invert +
     sn_weighted_gather_backward_inverted: the bits of the ordered route, without its (B,C,M,K) scratch buffer).  start / order: a
@@ -707,18 +734,15 @@ class ThreeInterpolateFunction(torch.autograd.Function):
         gX = torch.empty_like(X) if need_X else None
         gw = torch.empty_like(w) if need_w else None
         with torch.cuda.device(X.device):
-            if need_X and start is None and not gather_invert_supported(N, M * K):
+            inverse = _backward_inverse(idx, N, start, order) if need_X else None
+            if need_X and inverse is None:
                 scratch = torch.empty(B * C * M * K, device=X.device, dtype=torch.float32)
                 check(lib.sn_weighted_gather_backward_ordered(B, C, N, M, K, ptr(X), ptr(idx), ptr(w), ptr(grad_out), ptr(gw),
                                                               ptr(gX), ptr(scratch), _stream(X)), "sn_weighted_gather_backward_ordered")
                 return gX, None, gw, None, None
             if need_X:
-                if start is None:
-                    start = torch.empty(B, N + 1, device=X.device, dtype=torch.int32)
-                    order = torch.empty(B, M * K, device=X.device, dtype=torch.int32)
-                    check(lib.sn_gather_invert(B, N, M * K, ptr(idx), ptr(start), ptr(order), _stream(X)), "sn_gather_invert")
-                check(lib.sn_weighted_gather_backward_inverted(B, C, N, M, K, ptr(w), ptr(grad_out), ptr(start), ptr(order), ptr(gX),
-                                                               _stream(X)), "sn_weighted_gather_backward_inverted")
+                check(lib.sn_weighted_gather_backward_inverted(B, C, N, M, K, ptr(w), ptr(grad_out), ptr(inverse[0]), ptr(inverse[1]),
+                                                               ptr(gX), _stream(X)), "sn_weighted_gather_backward_inverted")
             if need_w:
                 check(lib.sn_weighted_gather_backward(B, C, N, M, K, ptr(X), ptr(idx), ptr(w), ptr(grad_out), ptr(gw), None,
                                                       _stream(X)), "sn_weighted_gather_backward")
@@ -737,18 +761,7 @@ def three_interpolate(features, idx, weight, inverse=None):
     if idx.dtype not in (torch.int32, torch.int64):
         raise ValueError("three_interpolate: idx must be int32 (or int64, converted), got %s" % idx.dtype)
     _one_device("three_interpolate", features, idx, weight)
-    if inverse is None:
-        return ThreeInterpolateFunction.apply(features, idx, weight, None, None)
-    start, order = inverse
-    b, m = features.shape[0], features.shape[2]
-    if not gather_invert_supported(m, idx.shape[1] * 3):
-        raise ValueError("three_interpolate: m = %d with %d entries per cloud is beyond sn_gather_invert_supported: no inverse exists "
-                         "for it (leave inverse=None for the ordered route)" % (m, idx.shape[1] * 3))
-    for t, shape, name in ((start, (b, m + 1), "start"), (order, (b, idx.shape[1] * 3), "order")):
-        if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("three_interpolate: inverse.%s must be contiguous int32 %s (ops.gather_invert(idx, %d)), got %s %s"
-                             % (name, shape, m, tuple(t.shape), t.dtype))
-    _one_device("three_interpolate", features, start, order)
+    start, order = _inverse_arg("three_interpolate", inverse, features.shape[0], features.shape[2], idx.shape[1] * 3, features)
     return ThreeInterpolateFunction.apply(features, idx, weight, start, order)
 
 
@@ -790,7 +803,8 @@ class InterpRowsFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             with torch.cuda.device(dev):
                 st = _stream(grad_rows)
-                if start is None and not gather_invert_supported(m, 3 * n):
+                inverse = _backward_inverse(idx, m, start, order)
+                if inverse is None:
                     # the ordered route reads and writes channel-major: the transposed slice in, the transposed gradient out
                     g = grad_rows[..., :c2].transpose(1, 2).contiguous()
                     X = known_rows.transpose(1, 2).contiguous()
@@ -800,8 +814,7 @@ class InterpRowsFunction(torch.autograd.Function):
                                                                   ptr(scratch), st), "sn_weighted_gather_backward_ordered")
                     gk = gX.transpose(1, 2).contiguous()
                 else:
-                    if start is None:
-                        start, order = gather_invert(idx, m)
+                    start, order = inverse
                     gk = torch.empty(b, m, c2, device=dev, dtype=torch.float32)
                     check(lib.sn_interp_rows_backward(b, n, m, c2, c1, ptr(weights), ptr(grad_rows), ptr(start), ptr(order), ptr(gk), st),
                           "sn_interp_rows_backward")
@@ -836,17 +849,7 @@ def interp_rows(known_rows, skip_rows, idx, dist2, rule="sqrt_eps", inverse=None
     if m == 0 and b * n > 0:
         raise ValueError("interp_rows: the known cloud is empty")
     _one_device("interp_rows", known_rows, skip_rows, idx, dist2)
-    start = order = None
-    if inverse is not None:
-        start, order = inverse
-        if not gather_invert_supported(m, n * 3):
-            raise ValueError("interp_rows: m = %d with %d entries per cloud is beyond sn_gather_invert_supported: no inverse exists "
-                             "for it (leave inverse=None for the ordered route)" % (m, n * 3))
-        for t, shape, name in ((start, (b, m + 1), "start"), (order, (b, n * 3), "order")):
-            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
-                raise ValueError("interp_rows: inverse.%s must be contiguous int32 %s (ops.gather_invert(idx, %d)), got %s %s"
-                                 % (name, shape, m, tuple(t.shape), t.dtype))
-        _one_device("interp_rows", known_rows, start, order)
+    start, order = _inverse_arg("interp_rows", inverse, b, m, n * 3, known_rows)
     return InterpRowsFunction.apply(known_rows, skip_rows, idx, dist2, INTERP_RULES[rule], start, order)
 
 
@@ -891,7 +894,9 @@ class BallGroupRowsFunction(torch.autograd.Function):
         gn = torch.empty(b, m, 3, device=dev, dtype=torch.float32) if need_new else None
         with torch.cuda.device(dev):
             st = _stream(grad_rows)
-            if (need_xyz or need_f) and not gather_invert_supported(n, m * ns):
+            # the lists are built only for the outputs that are sums over them ((need_xyz and u) or need_f)
+            inverse = _backward_inverse(idx, n) if (need_xyz and u) or need_f else None
+            if inverse is None and (need_xyz or need_f) and not gather_invert_supported(n, m * ns):
                 # the atomic route: sn_ball_group_backward reads channel-major and writes (B,C,N)
                 g = grad_rows.permute(0, 3, 1, 2).contiguous()
                 gf = torch.empty(b, c, n, device=dev, dtype=torch.float32) if need_f else None
@@ -899,9 +904,7 @@ class BallGroupRowsFunction(torch.autograd.Function):
                       "sn_ball_group_backward")
                 return gx, gn, (gf.transpose(1, 2).contiguous() if need_f else None), None, None, None, None
             gf = torch.empty(b, n, c, device=dev, dtype=torch.float32) if need_f else None
-            start = order = None
-            if (need_xyz and u) or need_f:
-                start, order = gather_invert(idx, n)
+            start, order = inverse or (None, None)
             check(lib.sn_group_rows_backward(b, n, m, c, ns, u, ptr(idx), ptr(start), ptr(order), ptr(grad_rows), ptr(gf), ptr(gx),
                                              ptr(gn), st), "sn_group_rows_backward")
         return gx, gn, gf, None, None, None, None

@@ -1,7 +1,8 @@
 """Test helper for the C-ABI contract tests (tests/test_gpu_cabi_contract.py, tests/test_cabi_arguments.py): plain fp64
 restatements of the geometric operations of include/samplenet_hip.h (softmax weights, weighted gather, index-add, the soft
 projection and its gradients, the simplification / Chamfer-mean losses, the PCRNet head, quaternion rotation), the input
-recipes the existing GPU tests use, and the poison-and-guard buffers that prove "overwritten" / "may be NULL" sentences.
+recipes the existing GPU tests use, the poison-and-guard buffers that prove "overwritten" / "may be NULL" sentences, and the small
+helpers every direct test of an entry point needs (stream, bits, invert).
 Lives in tests/ on purpose: nothing here is a product route."""
 import numpy as np
 import torch
@@ -116,6 +117,23 @@ def arg(x):
     if isinstance(x, torch.Tensor):
         return x.data_ptr()
     return x
+
+
+def stream():
+    """The current stream, as the entry points take it."""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def bits(a):
+    """float32 values as their int32 bit patterns: array_equal on these tells -0 from +0 and one NaN from another."""
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def invert(lib, b, n, ne, idx):
+    """sn_gather_invert of a device idx (b,ne) int32 into plain device buffers -> start (b,n+1), order (b,ne)."""
+    start, order = torch.empty(b, n + 1, device="cuda", dtype=torch.int32), torch.empty(b, ne, device="cuda", dtype=torch.int32)
+    assert lib.sn_gather_invert(b, n, ne, idx.data_ptr(), start.data_ptr(), order.data_ptr(), stream()) == 0
+    return start, order
 
 
 # ------------------------------------------------------------------------------------------------ fp64 references

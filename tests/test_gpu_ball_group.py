@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import ball_ref as R
-from cabi_ref import Guarded
+from cabi_ref import Guarded, bits as _bits, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +38,6 @@ def case(shape, recipe):
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _forward(lib, shape, c, u, radius, rule, dP, dQ, dF, with_cnt=True):

@@ -11,13 +11,9 @@ import pytest
 import torch
 
 import fp_rows_ref as FR
-from cabi_ref import Guarded
+from cabi_ref import Guarded, stream as _stream
 
 pytestmark = pytest.mark.gpu
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _run(lib, rows, C, z, coef, g):

@@ -7,17 +7,13 @@ import pytest
 import torch
 
 import gather_inv_ref as G
-from cabi_ref import UNSUPPORTED, Guarded
+from cabi_ref import UNSUPPORTED, Guarded, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _run(lib, b, n, ne, didx):

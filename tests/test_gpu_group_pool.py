@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import group_rows_ref as GR
-from cabi_ref import Guarded
+from cabi_ref import Guarded, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +33,6 @@ def case(G, S, C):
             a.setflags(write=False)
         _CASES[(G, S, C)] = (z, coef, g, ref)
     return _CASES[(G, S, C)]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _i32(t):

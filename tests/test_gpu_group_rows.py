@@ -15,7 +15,7 @@ import torch
 
 import ball_ref as R
 import group_rows_ref as GR
-from cabi_ref import Guarded
+from cabi_ref import Guarded, bits as _bits, invert as _invert, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -60,14 +60,6 @@ def cols(c, u):
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _forward(lib, shape, c, u, radius, rule, dP, dQ, dF, with_cnt=True):
@@ -143,12 +135,6 @@ def test_forward_pts_cnt_may_be_null_and_the_argument_errors():
     assert bad == [BAD_ARGUMENT] * len(bad)
     assert bwd(0, n, m, 5, ns, 1, None, None, None, None, None, None, None, st) == 0
     assert all(t.untouched() for t in (o, gi, gf, gx, gn, s_, o_))
-
-
-def _invert(lib, b, n, ne, idx):
-    start, order = torch.empty(b, n + 1, device="cuda", dtype=torch.int32), torch.empty(b, ne, device="cuda", dtype=torch.int32)
-    assert lib.sn_gather_invert(b, n, ne, idx.data_ptr(), start.data_ptr(), order.data_ptr(), _stream()) == 0
-    return start, order
 
 
 def _backward(lib, shape, c, u, idx, inv, g, want=(True, True, True)):

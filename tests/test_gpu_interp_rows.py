@@ -11,21 +11,13 @@ import torch
 
 import fp_rows_ref as FR
 import interp_ref as R
-from cabi_ref import Guarded
+from cabi_ref import Guarded, bits as _bits, invert as _invert, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _forward(lib, shape, rule, kr, sr, idx, d2):
@@ -80,12 +72,6 @@ def test_forward_clamps_a_foreign_index():
     w, rows = _forward(lib, shape, 0, kr, sr, idx, d2)
     w2, rows2 = _forward(lib, shape, 0, kr, sr, good, d2)
     assert torch.equal(w.check("w"), w2.check("w")) and torch.equal(rows.check("rows"), rows2.check("rows"))
-
-
-def _invert(lib, b, n, ne, idx):
-    start, order = torch.empty(b, n + 1, device="cuda", dtype=torch.int32), torch.empty(b, ne, device="cuda", dtype=torch.int32)
-    assert lib.sn_gather_invert(b, n, ne, idx.data_ptr(), start.data_ptr(), order.data_ptr(), _stream()) == 0
-    return start, order
 
 
 def _backward(lib, shape, w, g, start, order):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import interp_ref as R
+from cabi_ref import bits as _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -31,10 +32,6 @@ def case(recipe):
 
 def dev(a):
     return torch.tensor(a, device="cuda")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _within(got, ref, k, sab, what):

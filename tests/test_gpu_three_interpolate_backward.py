@@ -11,21 +11,13 @@ import pytest
 import torch
 
 import gather_inv_ref as G
-from cabi_ref import POISON, Guarded
+from cabi_ref import POISON, Guarded, bits as _bits, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _ok(lib, rc):

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import interp_ref as R
-from cabi_ref import Guarded
+from cabi_ref import Guarded, bits as _bits, stream as _stream
 
 pytestmark = pytest.mark.gpu
 _REF = {}
@@ -28,14 +28,6 @@ def case(shape, recipe):
 
 def dev(a):
     return torch.tensor(a, device="cuda")  # (a copy: the shared references are read-only)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def _run(lib, shape, du, dk, with_d2=True, with_d=True):
