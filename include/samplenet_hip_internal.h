@@ -459,6 +459,36 @@ int sn_classification_terms_forward(int B, int C, const float *logits, const int
                                     float *means, sn_stream_t stream);
 int sn_classification_terms_backward(int B, int C, const float *logits, const int *labels, const float *g_means, const float *g_ce,
                                      float *g_logits, sn_stream_t stream);
+/* The per-point (segmentation) loss and prediction terms (csrc/seg_terms.hip): torch's F.cross_entropy(weight=, ignore_index=) with
+ * reduction 'none' and 'mean', numpy's argmax, and the per-cloud, per-class counts accuracy and IoU are formed from.  The reference
+ * has no segmentation code: the yardstick is the fp64 restatement of tests/seg_terms_ref.py.  logits (R,C) fp32 with the C
+ * channels contiguous, R = clouds * rows_per_cloud; labels (R,) int32; class_weights (C,) or NULL (every weight 1).
+ *   A point is VALID when 0 <= label < C; every other label is IGNORED whatever its value (-100, -1, 255, C, ..): ce = 0, pred is
+ *   still written, the point enters no count and no mean and its gradient row is zero.  No label makes the kernels read outside
+ *   logits or class_weights.
+ *   ce[r]    = (logf(sum_c expf(x_c - m)) + m) - x_label, m = max_c x_c (unweighted).
+ *   pred[r]  = numpy's argmax: the FIRST maximum; if a logit is NaN, the index of the first NaN.
+ *   cloud_counts[b][c] (clouds,C,3) int32 = (points labelled c, valid points predicted c, valid points with pred == label == c),
+ *     exact, OVERWRITTEN (the entry clears it on the stream; the caller clears nothing).
+ *   means[0] = sum_valid w_label ce / sum_valid w_label (torch's reduction='mean' with weight=; NaN when no point is valid),
+ *   means[1] = correct / valid from integer counts with one division (0 when no point is valid),  means[2] = sum_valid w_label.
+ * On a valid row a NaN logit gives ce = NaN, a label whose logit is -inf gives +inf, a row of all -inf gives NaN (pred 0), C = 1
+ * gives ce = 0 exactly (sn_classification_terms_forward's rules).  Every output may be NULL: only what is asked for is computed
+ * and written.  `means` needs `workspace` (sn_segmentation_terms_workspace_bytes(R, C) bytes, -1 outside the range; no contents
+ * are kept between calls): the batch sums are per-workgroup partials in one fixed order, summed in workgroup order by a closing
+ * launch on the same stream -- no float atomics, no arrival counter: two runs are bit-identical.  The mapping and the order of
+ * every fp32 operation are written at the head of csrc/seg_terms.hip.
+ * _backward: g_logits (R,C), OVERWRITTEN,
+ *   g_logits[r][c] = (g_means[0] * w_label / means[2] + g_ce[r]) * (softmax(x_r)_c - [c == label_r]),
+ * the softmax recomputed (nothing is saved).  means: the forward's (only [2] is read, only with g_means); g_means: DEVICE pointer,
+ * only [0] is read, so a pointer to the one scalar serves; g_means and g_ce (R,) may each be NULL (the part is left out).
+ * Range: R >= 0, C >= 1, rows_per_cloud >= 1 dividing R, R * C < 2^31; R = 0 is a no-op; anything else is SN_ERR_BAD_ARGUMENT. */
+long long sn_segmentation_terms_workspace_bytes(long long R, int C);
+int sn_segmentation_terms_forward(long long R, int rows_per_cloud, int C, const float *logits, const int *labels,
+                                  const float *class_weights, float *ce, int *pred, int *cloud_counts, float *means, void *workspace,
+                                  sn_stream_t stream);
+int sn_segmentation_terms_backward(long long R, int C, const float *logits, const int *labels, const float *class_weights,
+                                   const float *means, const float *g_means, const float *g_ce, float *g_logits, sn_stream_t stream);
 /* sn_nn_matching (samplenet_hip.h) with the two products its kernel computed and dropped: out_idx (B,k) int32 = the indices of the
  * selected points in selection order -- the first occurrences in idx order, then the farthest-point picks: fps_from_given_indices'
  * idx, reconstruction/src/samplenet_pointnet_ae.py:515-533 -- and n_unique (B,) int32 = the number of distinct values of idx[b, :]

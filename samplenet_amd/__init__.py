@@ -16,8 +16,10 @@ from .progressive import SampleNetProgressive, progressive_sizes  # noqa: F401
 from .samplenet import SampleNet  # noqa: F401
 from .evaluation import (ClassificationEvaluator, ProgressiveClassificationEvaluator,  # noqa: F401
                          ProgressiveReconstructionEvaluator, ProgressiveRetrievalEvaluator, ReconstructionEvaluator,
-                         RegistrationEvaluator, RetrievalEvaluator, classification_aggregates, retrieval_aggregates)
+                         RegistrationEvaluator, RetrievalEvaluator, SegmentationEvaluator, classification_aggregates,
+                         retrieval_aggregates, segmentation_aggregates)
 from .samplers import FPSSampler, RandomSampler  # noqa: F401
+from .segmentation import segmentation_loss  # noqa: F401
 from .soft_projection import SoftProjection  # noqa: F401
 
 __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "SampleNet", "FPSSampler", "RandomSampler", "SampleNetProgressive",
@@ -25,4 +27,5 @@ __all__ = ["ChamferDistance", "ChamferDistanceFunction", "SoftProjection", "Samp
            "sputils", "ops", "optim", "BatchRecipe", "DeviceBatchSource", "DeviceCloudSet", "QuaternionTransform", "qinv", "rad_to_deg",
            "deg_to_rad", "RegistrationEvaluator", "ClassificationEvaluator", "ReconstructionEvaluator",
            "ProgressiveClassificationEvaluator", "ProgressiveReconstructionEvaluator", "classification_aggregates",
-           "RetrievalEvaluator", "ProgressiveRetrievalEvaluator", "retrieval_aggregates"]
+           "RetrievalEvaluator", "ProgressiveRetrievalEvaluator", "retrieval_aggregates", "SegmentationEvaluator",
+           "segmentation_aggregates", "segmentation_loss"]

@@ -62,6 +62,8 @@ SOURCES = [
     ("pose_terms.hip", ["-ffp-contract=off"]),
     # the classification terms: the same contract (tests/cls_terms_ref.py counts from the order written in the file)
     ("cls_terms.hip", ["-ffp-contract=off"]),
+    # the per-point segmentation terms: the same contract (tests/seg_terms_ref.py counts from the order written in the file)
+    ("seg_terms.hip", ["-ffp-contract=off"]),
     # the ball query's distance is difference, product, sum and one correctly rounded sqrt (tests/ball_ref.py restates it in fp32)
     ("ball_query.hip", ["-ffp-contract=off"]),
     # the three-NN distance is difference, product, sum in one written-out order (tests/interp_ref.py restates it in fp32)

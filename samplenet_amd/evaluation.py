@@ -584,3 +584,95 @@ class ProgressiveRetrievalEvaluator:
             r.update(retrieval_aggregates(r["ap"], r["prec"], out["n_relevant"]))
             out["by_size"][s] = r
         return out
+
+
+# ------------------------------------------------------------------------------------------------ segmentation
+def segmentation_aggregates(cloud_counts, means, categories=None, parts_of_category=None):
+    """The figures of a per-point evaluation from cloud_counts (clouds, C, 3) = per cloud and class (points labelled c, valid points
+    predicted c, valid points with pred == label == c) and the per-batch means (batches, 3) of ops.segmentation_terms, in int64 /
+    float64.  A point whose label lies outside [0, C) is ignored: it is in no count.  With L_c, P_c, T_c the three columns summed
+    over every cloud:
+        total_valid        = sum_c L_c
+        overall_accuracy   = sum_c T_c / total_valid                       (NaN without a valid point)
+        class_accuracies_c = T_c / L_c, and 0 for a class that is predicted but never labelled (L_c = 0 < P_c)
+        class_iou_c        = T_c / (L_c + P_c - T_c)
+        both are NaN for a class absent from labels AND predictions (L_c = P_c = 0), and such a class is left out of
+        mean_class_accuracy and miou, the plain means over the remaining classes (NaN when none remains)
+        mean_loss          = sum_j means_j[0] means_j[2] / sum_j means_j[2]: the weighted mean loss over all valid points of all
+                             batches (a batch without a valid point adds nothing)
+    With parts_of_category (category -> the class indices of its parts) and categories (clouds,), the ShapeNet-part figures: only the
+    cloud's own category's parts count; a part's IoU in a cloud is T / (L + P - T) of that cloud's counts and 1 when the part is
+    absent from both its labels and its predictions (L = P = 0); cloud_iou = the mean over the category's parts;
+    instance_miou = the mean of cloud_iou over the clouds; category_iou[k] = the mean of cloud_iou over the clouds of category k (NaN
+    for a category without a cloud); category_miou = the mean over the categories that have a cloud.  A prediction outside the
+    cloud's own parts is counted as it is: it belongs to no part of the category."""
+    counts = np.asarray(cloud_counts).astype(np.int64)
+    means = np.asarray(means, dtype=np.float64).reshape(-1, 3)
+    L, P, T = (counts[:, :, k].sum(0) for k in range(3))
+    present = (L + P) > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        acc = np.where(present, T / np.maximum(L, 1), np.nan)
+        iou = np.where(present, T / np.maximum(L + P - T, 1), np.nan)
+        total = int(L.sum())
+        den = means[:, 2]
+        num = np.where(den > 0, means[:, 0] * den, 0.0)
+        out = {"total_valid": total, "overall_accuracy": float(T.sum()) / total if total else float("nan"),
+               "class_labelled": L, "class_predicted": P, "class_correct": T, "class_accuracies": acc, "class_iou": iou,
+               "mean_class_accuracy": float(acc[present].mean()) if present.any() else float("nan"),
+               "miou": float(iou[present].mean()) if present.any() else float("nan"),
+               "mean_loss": float(num.sum() / den.sum()) if den.sum() > 0 else float("nan")}
+    if parts_of_category is not None:
+        cats = np.asarray(categories).astype(np.int64)
+        cloud_iou = np.empty(len(cats), dtype=np.float64)
+        for b, k in enumerate(cats):
+            parts = np.asarray(parts_of_category[int(k)], dtype=np.int64)
+            l, p, t = (counts[b, parts, j].astype(np.float64) for j in range(3))
+            union = l + p - t
+            cloud_iou[b] = np.where(union > 0, t / np.maximum(union, 1), 1.0).mean()
+        keys = sorted(parts_of_category)
+        cat_iou = np.array([cloud_iou[cats == k].mean() if (cats == k).any() else np.nan for k in keys])
+        out.update({"cloud_iou": cloud_iou, "instance_miou": float(cloud_iou.mean()), "category_iou": dict(zip(keys, cat_iou)),
+                    "category_miou": float(np.nanmean(cat_iou)) if np.isfinite(cat_iou).any() else float("nan")})
+    return out
+
+
+class SegmentationEvaluator:
+    """network: a per-point network, network(xyz (B,N,3), features (B,Cf,N) or None) -> logits (B,num_classes,N) or (B,N,num_classes)
+    (PointNet2SemSegSSG returns the first as a view of the second's memory, read without a copy); class_weights (num_classes,) or
+    None: the loss's weights; parts_of_category: {category: the class indices of its parts} for the ShapeNet-part figures (add then
+    takes the clouds' categories).  Labels outside [0, num_classes) are ignored points.  add() runs the network in eval mode under
+    no_grad and makes ONE ops.segmentation_terms call; the per-cloud counts and the loss pieces stay on the device, nothing
+    synchronises; result() makes one transfer and forms segmentation_aggregates (the definitions are in its docstring)."""
+
+    def __init__(self, network, num_classes, class_weights=None, parts_of_category=None):
+        self.network, self.num_classes = network, int(num_classes)
+        self.class_weights = class_weights
+        self.parts_of_category = None if parts_of_category is None else {int(k): tuple(int(p) for p in v)
+                                                                       for k, v in dict(parts_of_category).items()}
+        self.reset()
+
+    def reset(self):
+        self._got = _Collected()
+
+    def add(self, xyz, features, labels, categories=None):
+        """One batch: xyz (B,N,3), features (B,Cf,N) or None, labels (B,N) integer, categories (B,) integer (needed with
+        parts_of_category).  No synchronisation."""
+        ops._need_gpu(xyz, features, labels, categories)
+        if self.parts_of_category is not None and categories is None:
+            raise ValueError("SegmentationEvaluator.add: parts_of_category was given, so every batch needs its categories")
+        with _EvalMode(self.network), torch.no_grad():
+            logits = self.network(xyz, features)
+            if logits.dim() != 3 or self.num_classes not in (logits.shape[1], logits.shape[2]):
+                raise ValueError("SegmentationEvaluator.add: the network returned %s for %d classes" % (tuple(logits.shape), self.num_classes))
+            _ce, _pred, counts, means = ops.segmentation_terms(logits, labels, self.class_weights)
+            self._got.put("cloud_counts", counts, np.int64)
+            self._got.put("means", means.reshape(1, 3), np.float64)
+            if categories is not None:
+                self._got.put("categories", categories.clone(), np.int64)
+
+    def result(self):
+        """One device-to-host transfer -> dict: cloud_counts (clouds, num_classes, 3) int64, means (batches, 3) float64, categories when
+        given, and segmentation_aggregates of them."""
+        out = _need_added(self._got, "SegmentationEvaluator").fetch()
+        out.update(segmentation_aggregates(out["cloud_counts"], out["means"], out.get("categories"), self.parts_of_category))
+        return out

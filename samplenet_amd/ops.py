@@ -1722,3 +1722,123 @@ def classification_mean_loss(logits, labels):
     """classification_terms' means[0] alone, as a 0-d tensor differentiable in the logits: what classification_loss(fused=True) adds
     its regulariser to."""
     return ClassificationMeanLossFunction.apply(logits, labels.detach())
+
+
+# --------------------------------------------------------------------------------------------- segmentation terms
+def _seg_rows(logits, labels, who):
+    """-> (rows (B,N,C) float32 contiguous, transposed): logits given as (B,N,C), or as (B,C,N) when that is a transposed view of
+    contiguous (B,N,C) rows -- taken without a copy either way (pointnet2_modules._rows_of's rule)."""
+    if logits.dim() != 3 or labels.dim() != 2:
+        raise ValueError("%s: logits (B,N,C) or (B,C,N) and labels (B,N), got %s and %s" % (who, tuple(logits.shape), tuple(labels.shape)))
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    as_given = tuple(logits.shape[:2]) == tuple(labels.shape)
+    flipped = (logits.shape[0], logits.shape[2]) == tuple(labels.shape)
+    if as_given and (logits.is_contiguous() or not flipped or not logits.transpose(1, 2).is_contiguous()):
+        return logits.contiguous(), False
+    if flipped:
+        return logits.transpose(1, 2).contiguous(), True
+    raise ValueError("%s: logits %s do not go with labels %s" % (who, tuple(logits.shape), tuple(labels.shape)))
+
+
+def _seg_weights(class_weights, rows, who):
+    if class_weights is None:
+        return None
+    _need_gpu(class_weights)
+    if class_weights.dim() != 1 or class_weights.shape[0] != rows.shape[2]:
+        raise ValueError("%s: class_weights must be (%d,), got %s" % (who, rows.shape[2], tuple(class_weights.shape)))
+    return class_weights.detach().contiguous().float()
+
+
+def _seg_forward(rows, labels, weights, ce, pred, counts, means):
+    B, N, C = rows.shape
+    work = None
+    if means is not None:
+        work = torch.empty(max(1, lib.sn_segmentation_terms_workspace_bytes(B * N, C)), device=rows.device, dtype=torch.uint8)
+    with torch.cuda.device(rows.device):
+        check(lib.sn_segmentation_terms_forward(B * N, max(N, 1), C, ptr(rows), ptr(labels), ptr(weights), ptr(ce), ptr(pred), ptr(counts),
+                                                ptr(means), ptr(work), _stream(rows)), "sn_segmentation_terms_forward")
+
+
+def _seg_backward(rows, labels, weights, means, g_means, g_ce):
+    B, N, C = rows.shape
+    g_rows = torch.empty_like(rows)
+    with torch.cuda.device(rows.device):
+        check(lib.sn_segmentation_terms_backward(B * N, C, ptr(rows), ptr(labels), ptr(weights), ptr(means), ptr(g_means), ptr(g_ce),
+                                                 ptr(g_rows), _stream(rows)), "sn_segmentation_terms_backward")
+    return g_rows
+
+
+class SegmentationTermsFunction(torch.autograd.Function):
+    """logits (B,N,C) [or the (B,C,N) transposed view], labels (B,N), class_weights (C,) or None -> ce (B,N), pred (B,N) int32,
+    cloud_counts (B,C,3) int32, means (3,) -- sn_segmentation_terms_forward (the terms and the closing sum) / _backward, one launch.
+    Gradients flow to the logits through ce and means[0]; means[1] and means[2] are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weights):
+        _need_gpu(logits, labels)
+        rows, flipped = _seg_rows(logits, labels, "segmentation_terms")
+        weights = _seg_weights(class_weights, rows, "segmentation_terms")
+        labels = labels.contiguous().int()
+        B, N, C = rows.shape
+        ce = torch.empty(B, N, device=rows.device, dtype=torch.float32)
+        pred = torch.empty(B, N, device=rows.device, dtype=torch.int32)
+        counts = torch.empty(B, C, 3, device=rows.device, dtype=torch.int32)
+        means = torch.empty(3, device=rows.device, dtype=torch.float32)
+        _seg_forward(rows, labels, weights, ce, pred, counts, means)
+        ctx.save_for_backward(rows, labels, weights, means)
+        ctx.flipped = flipped
+        ctx.mark_non_differentiable(pred, counts)
+        ctx.set_materialize_grads(False)
+        return ce, pred, counts, means
+
+    @staticmethod
+    def backward(ctx, g_ce, _g_pred, _g_counts, g_means):
+        rows, labels, weights, means = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        if g_ce is None and g_means is None:
+            g_rows = torch.zeros_like(rows)
+        else:
+            c = lambda g: None if g is None else g.contiguous().float()  # noqa: E731
+            g_rows = _seg_backward(rows, labels, weights, means, c(g_means), c(g_ce))
+        return (g_rows.transpose(1, 2) if ctx.flipped else g_rows), None, None
+
+
+def segmentation_terms(logits, labels, class_weights=None):
+    """-> (ce (B,N), pred (B,N) int32, cloud_counts (B,C,3) int32, means (3,)): the per-point softmax cross-entropy (0 on an ignored
+    point: any label outside [0, C)), numpy's argmax of the logits, per cloud and class the counts (labelled, predicted, correct) over
+    the valid points, and (the weighted mean loss of F.cross_entropy(weight=), correct / valid, the sum of the valid points' weights).
+    logits: (B,N,C), or (B,C,N) when that is a transposed view of (B,N,C) rows (no copy).  Differentiable in ce and means[0] with
+    respect to the logits."""
+    return SegmentationTermsFunction.apply(logits, labels.detach(), class_weights)
+
+
+class SegmentationMeanLossFunction(torch.autograd.Function):
+    """segmentation_terms' means[0] alone as a 0-d tensor: the forward with no per-point output, and the backward with the upstream
+    SCALAR itself as g_means -- ClassificationMeanLossFunction's twin."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weights):
+        _need_gpu(logits, labels)
+        rows, flipped = _seg_rows(logits, labels, "segmentation_mean_loss")
+        weights = _seg_weights(class_weights, rows, "segmentation_mean_loss")
+        labels = labels.contiguous().int()
+        means = torch.empty(3, device=rows.device, dtype=torch.float32)
+        _seg_forward(rows, labels, weights, None, None, None, means)
+        ctx.save_for_backward(rows, labels, weights, means)
+        ctx.flipped = flipped
+        return means[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, labels, weights, means = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g_rows = _seg_backward(rows, labels, weights, means, g.contiguous().float(), None)
+        return (g_rows.transpose(1, 2) if ctx.flipped else g_rows), None, None
+
+
+def segmentation_mean_loss(logits, labels, class_weights=None):
+    """segmentation_terms' means[0] alone, as a 0-d tensor differentiable in the logits: what segmentation_loss(fused=True) returns."""
+    return SegmentationMeanLossFunction.apply(logits, labels.detach(), class_weights)
